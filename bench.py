@@ -7,6 +7,7 @@ reads that is already resident in HBM.  Default workload = BASELINE.json configs
 1 MI355X"), the configuration the north-star target is quoted on.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config config3|config2|config4|config5] [--reads M]
+                    [--dump-outputs DIR]
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); every rank counts its own
 contiguous shard of reads (weak scaling, no collective on the data path) and the dense counter
@@ -44,6 +45,20 @@ WORKLOAD_TEXT = {
     "config5": "CRISPR {20} vs 100k guides, 1% substitutions + 0.1% N, <=4 mismatches (BASELINE configs[4], per-GPU shard of 125M reads)",
     "config5z": "config5 with guide ranks drawn Zipf-like (P(k) ~ 1/k): the counter hot-spot variant of SURVEY.md 8(d)",
 }
+# --dump-outputs: rows are sampled by a seeded hash of their key, about DUMP_ROWS of them whatever the read count
+# (a config-3 step has ~10^8 rows); DUMP_MAX_ROWS keeps the files under 64 MB in any case
+DUMP_ROWS = 1 << 21
+DUMP_MAX_ROWS = 3_000_000
+DUMP_SEED = 0x5EED0B0C
+
+
+def mix64(x):
+    """splitmix64 finaliser over a uint64 array (wraps modulo 2^64)"""
+    import numpy as np
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
 
 
 def parse_args(argv=None):
@@ -57,6 +72,12 @@ def parse_args(argv=None):
                     help="reads of the CPU baseline's independent-context leg (the reference-structure leg takes the first 1.5 M)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the legs beside the headline (finish, end-to-end, ingest, the other configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64): "
+                         "outcome_counters (the step's outcome counters, in the order of COUNTER_NAMES), rows_total "
+                         "(number of rows, sum of their counts), rows_key / rows_count (a fixed, seeded sample of at most "
+                         "%d of the rows bc_engine_finish_stream hands over: dense table index and count, ascending by "
+                         "index).  Costs one host sync before the last timed step." % DUMP_MAX_ROWS)
     ap.add_argument("--selftest-one-gpu", action="store_true",
                     help="TEST ONLY (tests/test_gpu_multirank.py): the N > 1 path with every rank on device 0 -- the box has one "
                          "GPU --, torch.distributed on gloo and the engines' exchange over the message-file transport "
@@ -208,8 +229,9 @@ class Run:
     contract's numbers (rank 0: complete); the legs that are NOT part of the headline (finish, box ceilings, host
     submit, ingest) are separate methods that main() calls only after the contract line is out."""
 
-    def __init__(self, name, n, steps, warmup, world, rank, local, dev, comm=None, agree=None):
+    def __init__(self, name, n, steps, warmup, world, rank, local, dev, comm=None, agree=None, dump=False):
         self.agree, self.exchange_note = agree, ""  # agree(comm, why) -> (comm, note): see agree_on_transport
+        self.dump, self.last_step_outcomes = dump, None  # --dump-outputs: measure() keeps the last step's counters
         import torch
         import ngs_barcode_count_amd as pkg
         from ngs_barcode_count_amd import distributed as bcdist
@@ -242,13 +264,17 @@ class Run:
         free_b, _ = torch.cuda.mem_get_info(dev)
         reserve = (6 << 30) if world == 1 else (6 << 30) + 3 * w.plan.table_entries
         self.n_batches = int(max(1, min(steps, (free_b - reserve) // batch_bytes)))
-        first_read, _ = bcdist.shard(n * self.n_batches * world, rank, world)
+        # This rank's shard holds `steps` batches of the stream; batch k goes to slot k, except that the slot the last
+        # timed step reads gets batch steps - 1: the last step's reads do not depend on how many slots fit in HBM.
+        first_read, _ = bcdist.shard(n * steps * world, rank, world)
         self.first_read = first_read
+        last_slot = (steps - 1) % self.n_batches
         self.batches = []
         for k in range(self.n_batches):
+            b = steps - 1 if k == last_slot else k
             bs = torch.empty(n * R, dtype=torch.uint8, device=dev)
             bq = torch.empty(n * R, dtype=torch.uint8, device=dev) if self.with_qual else None
-            w.synth.generate_device(local, None, first_read + k * n, n, bs.data_ptr(), bq.data_ptr() if bq is not None else None)
+            w.synth.generate_device(local, None, first_read + b * n, n, bs.data_ptr(), bq.data_ptr() if bq is not None else None)
             self.batches.append((bs, bq))
         torch.cuda.synchronize()
 
@@ -317,7 +343,9 @@ class Run:
             carried[key] = 0
         self._barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for s in range(steps):
+            if self.dump and s == steps - 1:
+                before = eng.counters()  # (the outcome counters run on over the steps: where the last one starts)
             step()
         eng.sync()  # (a caller-owned table: folds the first-occurrence bits into it -- part of the job, inside the region)
         t_steps = time.perf_counter() - t0
@@ -347,10 +375,14 @@ class Run:
             # (the counters of the passes before a reset never went through the exchange: add them up separately)
             extra = self.comm.sum_u64([carried[k] for k in pkg.COUNTER_NAMES], 0)
             counters = {k: job_counters[k] + extra[i] for i, k in enumerate(pkg.COUNTER_NAMES)}
+            if self.dump:
+                before = dict(zip(pkg.COUNTER_NAMES, self.comm.sum_u64([before[k] for k in pkg.COUNTER_NAMES], 0)))
         else:
             counters = eng.counters()
             for key in carried:
                 counters[key] += carried[key]
+        if self.dump:
+            self.last_step_outcomes = [counters[k] - before[k] for k in pkg.COUNTER_NAMES]
         if rank != 0:
             return None
         total_reads = n * steps * world
@@ -399,6 +431,31 @@ class Run:
             except Exception as err:  # noqa: BLE001 -- a diagnostic never costs the measurement
                 res["table_rows_at_end"] = {"error": str(err)}
         return res
+
+    def dump_outputs(self, d):
+        """--dump-outputs (rank 0, straight after measure()): the last step's counters and rows as the caller of the
+        timed path receives them (bc_engine_counters, bc_engine_finish_stream), as float64 .npy files in d"""
+        import numpy as np
+        frac = min(1.0, DUMP_ROWS / (self.n * self.world))  # rows <= reads of the step
+        cut = np.uint64(int(frac * 2.0 ** 64)) if frac < 1.0 else None
+        keys, counts, total = [np.zeros(0, np.uint64)], [np.zeros(0, np.uint32)], [0, 0]
+
+        def on_rows(k, c):
+            total[0] += k.size
+            total[1] += int(c.sum(dtype=np.uint64))
+            if cut is not None:
+                keep = mix64(k ^ np.uint64(DUMP_SEED)) < cut
+                k, c = k[keep], c[keep]
+            keys.append(k)
+            counts.append(c)
+
+        self.eng.finish_stream(on_rows)
+        k, c = np.concatenate(keys), np.concatenate(counts)
+        order = np.argsort(k, kind="stable")[:DUMP_MAX_ROWS]
+        os.makedirs(d, exist_ok=True)
+        for name, a in (("outcome_counters", self.last_step_outcomes), ("rows_total", total), ("rows_key", k[order]),
+                        ("rows_count", c[order])):
+            np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))  # (keys < 2^53: exact)
 
     # ---- legs beside the headline (rank 0, N = 1), each called inside main()'s try/except ------------------------
     def leg_finish(self):
@@ -610,7 +667,7 @@ def main():
     agree = None
     if world > 1 and not one_gpu:
         agree = lambda c, why: agree_on_transport(dist, torch, pkg, dev, rank, world, c, why)  # noqa: E731
-    run = Run(args.config, n, args.steps, args.warmup, world, rank, local, dev, comm, agree)
+    run = Run(args.config, n, args.steps, args.warmup, world, rank, local, dev, comm, agree, dump=bool(args.dump_outputs))
     res = run.measure()
     exchange_note = run.exchange_note or exchange_note
     if rank != 0:
@@ -618,6 +675,8 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        run.dump_outputs(args.dump_outputs)
 
     crispr = args.config.startswith("config5")
     out = {
