@@ -465,6 +465,9 @@ __device__ __forceinline__ uint64_t map_slot(unsigned long long* __restrict__ sl
   }
 }
 
+// log mode (match_count_body): the slot of a read that is not counted through the log
+constexpr uint32_t kLogNone = 0xFFFFFFFFu;
+
 // a table add that also flags the entry's 256-byte block for the next reset (DevPlan::dirty_off; a plain byte store
 // of 1: idempotent, so no atomic is needed)
 __device__ __forceinline__ void table_add_marked(const DevPlan& pl, uint32_t* __restrict__ table, uint32_t* __restrict__ bits,
@@ -815,7 +818,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
                                                  unsigned long long* __restrict__ slots, uint32_t* __restrict__ vals,
                                                  uint64_t smask, unsigned long long* __restrict__ counters,
                                                  uint8_t* __restrict__ trace_outcome, uint64_t* __restrict__ trace_idx,
-                                                 uint32_t flags) {
+                                                 uint32_t flags, uint32_t* __restrict__ count_log = nullptr) {
   extern __shared__ uint4 smem[];
   __shared__ uint32_t s_cnt[kNCounters];
   const uint32_t tid = threadIdx.x;
@@ -901,6 +904,10 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   // Whichever way a read is counted the total stays exact (bit 0 -> 1, or table + 1), so the choice is free: a wave whose
   // probes mostly find their bit set already (a batch counted twice, a library seen many times over) goes straight to the
   // table for the next fifteen tiles and probes again on the sixteenth.
+  // Log mode (`count_log` given: dense plans with a bit map and 32-bit indexes): no counting atomic at all.  Every read
+  // of the batch gets one slot, written with one coalesced store per wave-tile -- its dense index when it is counted
+  // here, kLogNone otherwise -- and the fold kernels (bc_fold.h) apply the log to bit map + table after the kernel.
+  const bool logm = count_log != nullptr;
   uint32_t first_old = 0, first_on = 0, direct_tiles = 0;
   uint64_t first_idx = 0;
   uint64_t t = (uint64_t)blockIdx.x * (kTPB / 64) + wave;
@@ -999,7 +1006,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     // the previous tile's first-occurrence probes, before anything new is requested (what is still in flight now was
     // requested long ago): a bit that was set already makes the read a repeat, which goes to the table
     bool repeat = false;
-    if (bits) repeat = first_on != 0u && ((first_old >> ((uint32_t)first_idx & 31u)) & 1u) != 0u;
+    if (bits && !logm) repeat = first_on != 0u && ((first_old >> ((uint32_t)first_idx & 31u)) & 1u) != 0u;
     const uint64_t repeat_idx = first_idx;
     // the quality region is free: request the next tile's quality lines (they have until that tile's
     // quality stage to arrive)
@@ -1014,7 +1021,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     // when captures are kept raw, into the hash map slot of the tuple key.  Issued last so that the
     // fetches above are older: nothing in the next tile has to wait for the atomic to retire.
     ops.pending_add = 0;
-    if (bits) {
+    if (bits && !logm) {
       const uint32_t n_rep = (uint32_t)__popcll(__ballot(repeat));
       if (n_rep) {
         if (repeat) table_add_marked(pl, table, bits, repeat_idx);
@@ -1027,7 +1034,10 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     if (!pl.has_random) {
       bool add = active && outcome == kMatched && !pl.discard_counts && !(pl.abl() & 0x4u);
       if (hot && !pl.sparse && __any(add)) add = hot_count(add, (uint32_t)r.dense_idx);
-      if (__any(add)) {
+      if (logm) {
+        if (active) count_log[wfirst + lane] = add ? (uint32_t)r.dense_idx : kLogNone;
+        ops.pending_add += 1u;
+      } else if (__any(add)) {
         if (add) {
           if (pl.sparse) {
             atomicAdd(&vals[map_slot(slots, smask, r.dense_idx)], 1u);

@@ -29,17 +29,24 @@ done
 python3 - <<PY
 import csv, glob, collections, json
 agg = collections.defaultdict(list)
+fold = collections.defaultdict(float)  # log-mode counting: the fold kernels (bc_fold_*) of every submit, summed
 for f in glob.glob("$OUT/pmc_*/*/*counter_collection.csv"):
     for r in csv.DictReader(open(f)):
         if "match_count" in r["Kernel_Name"]:
             agg[r["Counter_Name"]].append(float(r["Counter_Value"]))
+        elif "bc_fold_" in r["Kernel_Name"]:
+            fold[r["Counter_Name"]] += float(r["Counter_Value"])
 out = {k: {"dispatches": len(v), "mean_per_dispatch": sum(v) / len(v)} for k, v in sorted(agg.items())}
 g = lambda k: out.get(k, {}).get("mean_per_dispatch")
+gf = lambda k: fold[k] / out[k]["dispatches"] if k in fold and k in out else 0.0  # per submit (= per match dispatch)
 f, w = g("FETCH_SIZE"), g("WRITE_SIZE")
 if f is not None and w is not None:
+    ff, fw = gf("FETCH_SIZE"), gf("WRITE_SIZE")
     out["hbm_traffic_bytes_per_dispatch"] = {
-        "fetch_corrected_x2": f * 1024 * 2, "write": w * 1024, "total": f * 1024 * 2 + w * 1024,
-        "note": "FETCH_SIZE/WRITE_SIZE are KB; gfx950 FETCH_SIZE reports 1/2 of the bytes of wide coalesced reads "
+        "fetch_corrected_x2": (f + ff) * 1024 * 2, "write": (w + fw) * 1024, "total": (f + ff) * 1024 * 2 + (w + fw) * 1024,
+        "fold_kernels_fetch_corrected_x2": ff * 1024 * 2, "fold_kernels_write": fw * 1024,
+        "note": "per submit: the match kernel + the fold kernels of log-mode counting (bc_fold_*, none on the atomic path); "
+                "FETCH_SIZE/WRITE_SIZE are KB; gfx950 FETCH_SIZE reports 1/2 of the bytes of wide coalesced reads "
                 "(MI355X_MICROARCH.md, HBM), so it is doubled; the scattered 4-byte atomics are uncalibrated"}
 if g("SQ_WAVE_CYCLES") and g("SQ_BUSY_CYCLES"):
     d = {}
