@@ -268,6 +268,10 @@ int bc_engine_kernel_ms_each(bc_engine *e, double *ms_out, uint64_t capacity, ui
 /* Which kernel the last submit launched: "match_count_kernel<NW,NWW>" (the generic one, any plan) or
  * "bc_jit_match_count<NW,NWW>" (the one specialised to this plan's scheme); "" before the first submit. */
 const char *bc_engine_kernel_name(bc_engine *e);
+/* How many times the engine has folded a count log into its counters since it was created (log-mode counting: dense
+ * plans with a bit map, BC_COUNT_LOG); 0 when every submit counted with per-read atomics.  One fold per chunk of at
+ * most BC_COUNT_LOG_CHUNK reads of a log-mode submit.  Read-only: does not wait for the device. */
+int bc_engine_count_log_folds(const bc_engine *e, uint64_t *n);
 /* Shader clock right now (MHz), measured by a 0.3 ms probe kernel on the engine's stream against the
  * 100 MHz reference counter.  Call it straight after the work of interest: the clock sags under power
  * and thermal limits, and the match kernel's time follows it. */

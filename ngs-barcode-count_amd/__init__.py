@@ -232,6 +232,12 @@ class Engine:
     def kernel_name(self):
         return self._lib.bc_engine_kernel_name(self._e).decode()
 
+    def count_log_folds(self):
+        """folds of a count log into the counters since the engine was created (0: every read counted atomically)"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_count_log_folds(self._e, C.byref(n)))
+        return n.value
+
     def sclk_mhz(self):
         """shader clock right now (0.3 ms probe kernel)"""
         v = C.c_double()

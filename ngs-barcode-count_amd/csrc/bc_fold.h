@@ -240,4 +240,34 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
   }
 }
 
+// The fold's launch sequence, on `stream`: the engine's fold_log() and the tests' harness (tests/fold) both call it.
+// log: n entries; grouped: room for n; meta: [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each, with
+// cnt all zero (the fold leaves it so); nb: buckets (ceil(entries / 2^22), at most kFoldMaxBuckets); n_words: bit-map
+// words in use; dirty: the table's dirty-block map, or null.  scatter_grid / apply_grid: 0 = sized from n_cus as the
+// engine does; tests force other counts to vary how tiles and items interleave.
+inline hipError_t fold_launch(hipStream_t stream, const uint32_t* log, uint64_t n, uint32_t* grouped, uint32_t* meta,
+                              uint32_t nb, uint32_t* bits, uint64_t n_words, uint32_t* table, uint8_t* dirty, uint32_t n_cus,
+                              uint32_t scatter_grid = 0, uint32_t apply_grid = 0) {
+  uint32_t* cnt = meta;
+  uint32_t* start = cnt + kFoldMaxBuckets + 1;
+  uint32_t* cursor = start + kFoldMaxBuckets + 1;
+  uint32_t* item_off = cursor + kFoldMaxBuckets + 1;
+  const uint64_t hist_cap = 4ull * n_cus, hist_want = (n / 4 + kFoldTPB - 1) / kFoldTPB + 1;
+  const uint64_t hist_grid = hist_want < hist_cap ? hist_want : hist_cap;
+  hipLaunchKernelGGL(bc_fold_hist, dim3((uint32_t)hist_grid), dim3(kFoldTPB), 0, stream, log, n, nb, cnt);
+  hipLaunchKernelGGL(bc_fold_scan, dim3(1), dim3(kFoldTPB), 0, stream, cnt, nb, start, cursor, item_off);
+  hipError_t rc = hipFuncSetAttribute((const void*)bc_fold_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFoldScatterLds);
+  if (rc != hipSuccess) return rc;
+  rc = hipFuncSetAttribute((const void*)bc_fold_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFoldApplyLds);
+  if (rc != hipSuccess) return rc;
+  const uint64_t tiles = (n + kFoldTile - 1) / kFoldTile, scatter_cap = 2ull * n_cus;
+  if (!scatter_grid) scatter_grid = (uint32_t)(tiles < scatter_cap ? tiles : scatter_cap);
+  hipLaunchKernelGGL(bc_fold_scatter, dim3(scatter_grid), dim3(kFoldTPB), kFoldScatterLds, stream, log, n, nb, cursor, grouped);
+  const uint64_t items_max = (n + kFoldChunk - 1) / kFoldChunk + nb;
+  if (!apply_grid) apply_grid = (uint32_t)(items_max < n_cus ? items_max : n_cus);
+  hipLaunchKernelGGL(bc_fold_apply, dim3(apply_grid), dim3(kFoldTPB), kFoldApplyLds, stream, (const uint32_t*)grouped, nb,
+                     (const uint32_t*)start, (const uint32_t*)item_off, bits, n_words, table, dirty);
+  return hipGetLastError();
+}
+
 }  // namespace bc

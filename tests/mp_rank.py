@@ -58,7 +58,7 @@ def main():
         rows = eng.result_rows()
         assert len(rows) == n_rows
         with open(out, "w") as f:
-            json.dump({"counters": counters, "rows": rows}, f)
+            json.dump({"counters": counters, "rows": rows, "log_folds": eng.count_log_folds()}, f)
     else:
         assert n_rows == 0 and not any(counters.values())
     comm.barrier()

@@ -199,6 +199,53 @@ def test_records_straddling_ingest_chunks(tmp_path, monkeypatch, chunk, name):
     assert {k: got[k] for k in o.counters} == o.counters and rows == o.rows()
 
 
+def test_log_counting_writes_what_atomic_counting_writes(tmp_path, monkeypatch):
+    """variable-length reads, records straddling 4 KiB ingest chunks: the command line's files with log-mode counting
+    forced are those of per-read atomics -- the same files, each header byte for byte, the same rows (their order
+    within a file is the compaction's, which differs from run to run in either mode), the stats file byte for byte up
+    to its clock lines -- and the same file counted through the ABI really went through the log"""
+    from test_gpu_parity import make_plan
+    c = cases.build_case("fmtn", seed=53, n=2500)
+    tmp = str(tmp_path)
+    args = write_inputs(tmp, c)
+    assert len({len(s) for s, _ in c["reads"]}) > 1
+    outs = {}
+    for mode in ("0", "1"):
+        out = os.path.join(tmp, "out" + mode)
+        os.makedirs(out)
+        env = dict(os.environ, BC_COUNT_LOG=mode, BC_BITMAP_MIN_ENTRIES="1", BC_INGEST_CHUNK="4096")
+        res = subprocess.run([CLI] + args + ["-o", out, "-p", "run1", "-m", "-e"], capture_output=True, text=True, env=env)
+        assert res.returncode == 0, res.stderr + res.stdout
+        outs[mode] = {f: open(os.path.join(out, f), "rb").read() for f in sorted(os.listdir(out))}
+    assert sorted(outs["0"]) == sorted(outs["1"]) and len(outs["0"]) > 2
+    o = parity.oracle_for(c)
+    for s, q in c["reads"]:
+        o.process(s, q)
+    clock = re.compile(rb"^(Start|Finish|Total time).*$", re.M)
+    for f, data in outs["0"].items():
+        if f.endswith("_barcode_stats.txt"):
+            assert clock.sub(b"", data) == clock.sub(b"", outs["1"][f]), f
+        elif ".all." in f:  # (the merged file: sample columns compared by name, as in test_cli_outputs)
+            h = [read_csv(os.path.join(tmp, "out" + m, f)) for m in ("0", "1")]
+            assert canonical(*h[0], o.barcode_num) == canonical(*h[1], o.barcode_num), f
+        else:
+            a, b = data.split(b"\n"), outs["1"][f].split(b"\n")
+            assert a[0] == b[0] and a[-1] == b[-1] == b"", f
+            assert sorted(a[1:-1]) == sorted(b[1:-1]), f
+    fq = args[args.index("-f") + 1]
+    monkeypatch.setenv("BC_INGEST_CHUNK", "4096")
+    monkeypatch.setenv("BC_BITMAP_MIN_ENTRIES", "1")
+    for mode in ("0", "1"):
+        import ngs_barcode_count_amd as pkg
+        monkeypatch.setenv("BC_COUNT_LOG", mode)
+        eng = pkg.Engine(make_plan(c), device=0)
+        assert eng.count_fastq(fq) == len(c["reads"])
+        got = eng.counters()
+        assert {k: got[k] for k in o.counters} == o.counters and eng.result_rows() == o.rows()
+        assert (eng.count_log_folds() > 0) == (mode == "1"), eng.count_log_folds()
+        eng.close()
+
+
 def test_file_sizes_around_a_chunk_multiple_and_missing_final_newline(tmp_path, monkeypatch):
     """end-of-file accounting (input.rs:44, 86, 128-130): a last record without its final newline is a whole record on
     the plain path; file lengths just below, at and just above a multiple of the chunk size"""

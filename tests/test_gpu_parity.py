@@ -86,6 +86,22 @@ def check_kernel(eng, kernel):
 @pytest.mark.parametrize("use_lens", [False, True])
 @pytest.mark.parametrize("kernel", ["generic", "specialised"], indirect=True)
 def test_engine_vs_oracle(name, use_lens, kernel):
+    _engine_vs_oracle(name, use_lens, kernel, "atomic")
+
+
+@pytest.mark.parametrize("name", NO_RANDOM)
+@pytest.mark.parametrize("use_lens", [False, True])
+@pytest.mark.parametrize("kernel", ["generic", "specialised"], indirect=True)
+def test_engine_vs_oracle_log_counting(name, use_lens, kernel, monkeypatch):
+    """the same reads with log-mode counting forced (BC_COUNT_LOG=1 and the bit map for every table size): per-read
+    parity and rows as they were, and the log really ran -- or, where the plan does not allow it (raw-capture keys, no
+    counts kept), did not"""
+    monkeypatch.setenv("BC_BITMAP_MIN_ENTRIES", "1")
+    monkeypatch.setenv("BC_COUNT_LOG", "1")
+    _engine_vs_oracle(name, use_lens, kernel, "log")
+
+
+def _engine_vs_oracle(name, use_lens, kernel, counting):
     c = cases.build_case(name, seed=11 + use_lens, n=3000)
     if not use_lens:
         rl = min(len(s) for s, _ in c["reads"])
@@ -102,6 +118,11 @@ def test_engine_vs_oracle(name, use_lens, kernel):
     assert got["total_reads"] == len(c["reads"]) and got["unsupported_reads"] == 0
     assert eng.result_rows() == o.rows()
     check_kernel(eng, kernel)
+    log_plan = plan.mode == "dense" and not discard and plan.table_entries > 0
+    if counting == "log" and log_plan:
+        assert eng.count_log_folds() == 1
+    else:
+        assert eng.count_log_folds() == 0
     eng.close()
 
 
@@ -134,8 +155,29 @@ def test_random_barcode_engine_vs_oracle(name, kernel):
     assert g2["matched"] == o.counters["matched"]
     assert g2["duplicates"] == 2 * o.counters["duplicates"] + o.counters["matched"]
     assert eng2.result_rows() == o.rows()
+    assert eng.count_log_folds() == 0 and eng2.count_log_folds() == 0
     eng.close()
     eng2.close()
+
+
+@pytest.mark.parametrize("name", ["rnd_rb_0", "rnd_rb_3"])
+def test_random_barcode_plans_refuse_log_counting(name, monkeypatch):
+    """log mode forced on: plans with a random barcode count distinct keys in a hash set, never through the log"""
+    monkeypatch.setenv("BC_BITMAP_MIN_ENTRIES", "1")
+    monkeypatch.setenv("BC_COUNT_LOG", "1")
+    c = cases.build_case(name, seed=21, n=4000)
+    plan = make_plan(c)
+    seq, qual, lens = readgen.to_arrays(c["reads"])
+    stride = seq.shape[1]
+    eng, _, _ = run_device(plan, seq, qual, lens, stride, stride)
+    o = parity.oracle_for(c)
+    for s, q in c["reads"]:
+        o.process(s, q)
+    got = eng.counters()
+    assert {k: got[k] for k in o.counters} == o.counters
+    assert eng.result_rows() == o.rows()
+    assert eng.count_log_folds() == 0
+    eng.close()
 
 
 @pytest.mark.parametrize("seed", range(16))

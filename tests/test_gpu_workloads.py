@@ -144,6 +144,22 @@ def test_config5_queued_searches_carry_over_between_tiles():
     through several tiles, so captures wait in its queue from one tile to the next and the read a verdict belongs to
     is found again from (tile, lane) -- every read's outcome against the oracle (an outcome slot nobody writes shows
     as 0xFF), then the rows"""
+    eng = _queued_searches_carry_over()
+    assert eng.count_log_folds() == 0  # (a 100 k-entry table: per-read atomics)
+    eng.close()
+
+
+def test_config5_queued_searches_carry_over_in_log_mode(monkeypatch):
+    """the same with log-mode counting forced: the queue's settled searches add to the table directly while the
+    launch's other reads go through the log"""
+    monkeypatch.setenv("BC_BITMAP_MIN_ENTRIES", "1")
+    monkeypatch.setenv("BC_COUNT_LOG", "1")
+    eng = _queued_searches_carry_over()
+    assert eng.count_log_folds() == 1
+    eng.close()
+
+
+def _queued_searches_carry_over():
     import torch
     import ngs_barcode_count_amd as pkg
     w = workloads.make("config5")
@@ -169,7 +185,7 @@ def test_config5_queued_searches_carry_over_between_tiles():
     guides = [g.decode() if isinstance(g, bytes) else g for g in w.counted[0]]
     assert sum(by_seq.values()) == int(hist.sum())
     assert all(by_seq.get(guides[g], 0) == int(c) for g, c in enumerate(hist))
-    eng.close()
+    return eng
 
 
 def test_config4_bench_variant_vs_oracle():
