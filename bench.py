@@ -7,7 +7,7 @@ reads that is already resident in HBM.  Default workload = BASELINE.json configs
 1 MI355X"), the configuration the north-star target is quoted on.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config config3|config2|config4|config5] [--reads M]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-extra] [--cpu-sample S]]
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); every rank counts its own
 contiguous shard of reads (weak scaling, no collective on the data path) and the dense counter
@@ -15,12 +15,15 @@ tables are sum-reduced ONCE with RCCL inside the timed region, as the job would 
 Under torchrun (WORLD_SIZE set) this process is one rank; started plainly with --gpus N > 1 it
 starts the N ranks itself as child processes -- before anything here has touched a GPU -- and
 passes rank 0's line through.
-Prints ONE JSON line on rank 0 (stdout), as soon as the timed region, the box's copy rate and the CPU baseline are done:
-the contract's fields, `roofline` (dominant kernel, HIP events on the engine's stream; per-launch first / median / last),
-`cpu_baseline`, `box`, `reset_ms`.  Only then, at N = 1, the legs beside the headline run, each on its own and with its
-failure recorded instead of raised: `finish` (table -> sparse rows on the host), `end_to_end` (host buffers -> counts
-over PCIe), `ingest` (FASTQ file -> counts) and `extra` (the other BASELINE configs, each with its own roofline).  They
-go to stderr as one `BENCH_EXTRA {...}` line and to gpurun_out/bench_extra.json -- never to stdout.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs if given, and ONE JSON
+line on rank 0 (stdout) with the contract's fields, `roofline` (dominant kernel, HIP events on the engine's stream
+during the timed steps; per-launch first / median / last), `outcomes` and `reset_ms`.
+--full adds, at N = 1, what takes runs of its own: `table_rows_at_end` (one sweep of the table), `box` (the box's copy
+rate and random-atomic rate) and `cpu_baseline` (--no-cpu: without it) in the line; then, after the line, the legs
+beside the headline, each on its own and with its failure recorded instead of raised (--no-extra: none of them):
+`finish` (table -> sparse rows on the host), `end_to_end` (host buffers -> counts over PCIe), `ingest` (FASTQ file ->
+counts) and `extra` (the other BASELINE configs, each with its own roofline).  They go to stderr as one
+`BENCH_EXTRA {...}` line and to bench_extra.json (emit_extras) -- never to stdout.
 """
 import argparse
 import json
@@ -68,10 +71,16 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="config3", choices=sorted(DEFAULT_READS))
     ap.add_argument("--reads", type=int, default=0, help="reads per step per GPU (default: the config's size)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (N = 1): rows in the table at the end, the box's "
+                         "copy and atomic rates, the CPU baseline, and the legs beside the headline (finish, end-to-end, "
+                         "ingest, the other configs)")
     ap.add_argument("--cpu-sample", type=int, default=4_000_000,
-                    help="reads of the CPU baseline's independent-context leg (the reference-structure leg takes the first 1.5 M)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs beside the headline (finish, end-to-end, ingest, the other configs)")
+                    help="--full: reads of the CPU baseline's independent-context leg (the reference-structure leg takes "
+                         "the first 1.5 M)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="--full: skip the legs beside the headline (finish, end-to-end, ingest, the other configs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64): "
                          "outcome_counters (the step's outcome counters, in the order of COUNTER_NAMES), rows_total "
@@ -227,7 +236,7 @@ def selftest_cpu(args, world, rank):
 class Run:
     """One BASELINE config on this rank's GPU: resident batches, an engine, the timed steps.  measure() returns the
     contract's numbers (rank 0: complete); the legs that are NOT part of the headline (finish, box ceilings, host
-    submit, ingest) are separate methods that main() calls only after the contract line is out."""
+    submit, ingest) are separate methods that main() calls only under --full."""
 
     def __init__(self, name, n, steps, warmup, world, rank, local, dev, comm=None, agree=None, dump=False):
         self.agree, self.exchange_note = agree, ""  # agree(comm, why) -> (comm, note): see agree_on_transport
@@ -289,7 +298,8 @@ class Run:
         if self.world > 1:
             self.torch.distributed.barrier()
 
-    def measure(self):
+    def measure(self, table_rows=False):
+        """the warm-up and the timed steps; table_rows (--full): also count the rows the table holds at the end"""
         torch, pkg, eng, w = self.torch, self.pkg, self.eng, self.w
         dist = torch.distributed
         n, R, steps, world, rank, dev = self.n, self.R, self.steps, self.world, self.rank, self.dev
@@ -424,7 +434,7 @@ class Run:
                "reset_in_region_ms": len(resets) * reset_ms,
                "value": total_reads / elapsed, "ms_per_step": elapsed * 1e3 / steps, "reduce_ms": reduce_ms,
                "reset_ms": reset_ms, "outcomes": {k: counters[k] for k in pkg.COUNTER_NAMES}, "roofline": roof}
-        if not self.random_mode and world == 1 and w.plan.table_entries:
+        if table_rows and not self.random_mode and world == 1 and w.plan.table_entries:
             try:  # rows the table holds at the end of the region (since the last reset): one sweep of the table
                 res["table_rows_at_end"] = eng.nonzero_entries()
                 res["table_entries"] = w.plan.table_entries
@@ -668,7 +678,7 @@ def main():
     if world > 1 and not one_gpu:
         agree = lambda c, why: agree_on_transport(dist, torch, pkg, dev, rank, world, c, why)  # noqa: E731
     run = Run(args.config, n, args.steps, args.warmup, world, rank, local, dev, comm, agree, dump=bool(args.dump_outputs))
-    res = run.measure()
+    res = run.measure(table_rows=args.full)
     exchange_note = run.exchange_note or exchange_note
     if rank != 0:
         run.close()
@@ -707,7 +717,8 @@ def main():
     for k in ("table_rows_at_end", "table_entries"):
         if k in res:
             out[k] = res[k]
-    if world == 1:
+    full = args.full and world == 1  # (what --full adds runs at N = 1 only, on rank 0)
+    if full:
         try:  # this box's copy rate (5 copies of 2 GiB: 10 ms): the headline's second denominator
             box = run.leg_box()
             out["box"] = box
@@ -715,16 +726,16 @@ def main():
             out["roofline"]["frac_of_box_copy"] = out["roofline"]["achieved"] / box["copy_GBps"] if box.get("copy_GBps") else None
         except Exception as err:  # noqa: BLE001 -- nothing beside the timed region may cost the line
             out["box"] = {"error": repr(err)}
-    if not args.no_cpu and world == 1:  # (rank 0 at N = 1 only: the contract's baseline leg)
+    if full and not args.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baselines(run.w, min(args.cpu_sample, n), max(2, min(os.cpu_count() or 2, 16)))
         except Exception as err:  # noqa: BLE001
             out["cpu_baseline"] = {"error": repr(err)}
-    # ---- the contract line: out before anything optional runs ---------------------------------------------------
+    # ---- the contract line: out before the legs beside the headline run ----------------------------------------
     print(json.dumps(out))
     sys.stdout.flush()
 
-    if world == 1 and not args.no_extra:
+    if full and not args.no_extra:
         extras = {"of": {"config": args.config, "steps": args.steps, "warmup": args.warmup}}
 
         def leg(name, fn):
