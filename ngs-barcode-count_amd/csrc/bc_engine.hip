@@ -7,23 +7,13 @@
 // global atomic per matched read into the dense (sample, barcode tuple) counter table that
 // stands in for Results' nested HashMap (info.rs:661-665).
 #include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
 #include <string.h>
-#include <dlfcn.h>
-#include <errno.h>
-#include <fcntl.h>
-#include <spawn.h>
-#include <sys/wait.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <functional>
-#include <map>
-#include <memory>
 #include <thread>
 #include <string>
 #include <vector>
@@ -31,10 +21,9 @@
 #include "../../include/barcode_count_hip.h"
 #include "bc_kernel.h"
 #include "bc_fold.h"
+#include "bc_jit.h"
 #include "bc_plan.hpp"
 #include "bc_synth.h"
-
-#include "bc_jit_sources.inc"  // the device headers as strings (generated by the Makefile)
 
 extern "C" int bc_internal_table_pack_u8(const void* d_table_u32, const void* d_bits, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64,
                                          void* d_ovf_val_u32, uint64_t ovf_capacity, uint64_t* n_ovf, int device_id, void* hip_stream);
@@ -632,25 +621,13 @@ struct bc_engine {
   size_t stage_bytes = 0;
   uint32_t lds_limit = 0;
   uint32_t n_cus = 0;
-  // scheme-specialised kernels, one per kernel shape (NW, NWW, lengths, tables, tracing)
-  struct Jit {
-    enum { kIdle = 0, kCompiling = 1, kCodeReady = 2, kLoaded = 3, kFailed = -1 };
-    std::atomic<int> state{kIdle};
-    std::thread worker;      // compiles in the background while the generic kernel keeps counting
-    std::vector<char> code;  // written by the worker before it publishes kCodeReady
-    std::string log;
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
-    int per_cu = 0;
-    bool scratch = false;  // the last load was refused because the build used scratch memory
-  };
-  std::map<uint64_t, std::unique_ptr<Jit>> jit;
+  JitKernels jit;  // scheme-specialised kernels, one per kernel shape (NW, NWW, lengths, tables, tracing)
   uint64_t reads_seen = 0;  // reads submitted so far: a cache miss is only worth a compile for a long run
   int jit_mode = 1;  // BC_JIT = 0: never | 1 (default): cache hit -> at once, else compiled in the background once 2^20
                      // reads have been seen | force (2): always, compiled synchronously | cached (3): cache hits only
   std::string last_kernel;
   bool pipe = true;   // software-pipelined tile fetch (BC_PIPE=0|1)
-  int lhash_mode = 1; // LDS exact-match tables: 0 never, 1 in the specialised kernel, 2 in both (BC_LHASH=0|1|2)
+  int lhash_mode = 1; // LDS exact-match tables (PlanSetup::lhash_mode)
   // random-barcode mode: the hash set of (tuple, random barcode) keys
   unsigned long long* d_slots = nullptr;
   uint32_t* d_vals = nullptr;  // sparse plans without a random barcode: the count of each key
@@ -691,10 +668,6 @@ static void engine_free(bc_engine* e) {
     if (e->dev[s]) (void)hipFree(e->dev[s]);
     if (e->copied[s]) (void)hipEventDestroy(e->copied[s]);
     if (e->consumed[s]) (void)hipEventDestroy(e->consumed[s]);
-  }
-  for (auto& kv : e->jit) {
-    if (kv.second->worker.joinable()) kv.second->worker.join();
-    if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
   }
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->own_table && e->d_table) (void)hipFree(e->d_table);
@@ -781,9 +754,12 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
   }
 
   DevPlan& P = e->h.plan;
-#ifdef BC_EXPERIMENT
-  if (const char* ab = getenv("BC_ABLATE")) P.ablate = (uint32_t)strtoul(ab, nullptr, 0);
-#endif
+  // the plan edits and bit-map layout an ahead-of-time build applies too
+  const PlanSetup ps = plan_setup(e->h, e->long_only, table_mem == nullptr);
+  e->lhash_mode = ps.lhash_mode;
+  e->n_bit_words = ps.n_bit_words;
+  e->dirty_bytes = ps.dirty_bytes;
+  e->table_entries = P.sparse ? 0 : e->h.table_entries;
   if (const char* jm = getenv("BC_JIT"))
     e->jit_mode = !strcmp(jm, "force") ? 2 : (!strcmp(jm, "0") ? 0 : (!strcmp(jm, "cached") ? 3 : 1));
   for (uint32_t g = 0; g < P.n_groups; ++g) {
@@ -824,9 +800,6 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
       G.dtable_a = (uint64_t)(uintptr_t)d;
     }
   }
-#ifdef BC_EXPERIMENT
-  if (const char* lh = getenv("BC_LHASH")) e->lhash_mode = atoi(lh);
-#endif
   if (const char* cl = getenv("BC_COUNT_LOG")) e->count_log = strcmp(cl, "auto") == 0 ? 2 : atoi(cl);
   if (const char* ch = getenv("BC_COUNT_LOG_HOT")) e->log_hot = atoi(ch) != 0;
   if (const char* cm = getenv("BC_COUNT_LOG_MIN_READS")) e->log_min_reads = strtoull(cm, nullptr, 0);
@@ -834,34 +807,12 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
     const uint64_t c = strtoull(cc, nullptr, 0) & ~63ull;
     if (c) e->log_chunk = std::min<uint64_t>(c, 1ull << 27);
   }
-  if (e->lhash_mode == 0) {
-    P.lhash_vec = 0;
-    for (uint32_t g = 0; g < P.n_groups; ++g) P.groups[g].lhash_nb = 0;
-  }
   if (P.lhash_vec) {
     const int rc = upload(e, e->h.lhash.data(), e->h.lhash.size() * 4, &P.lhash_a);
     if (rc) return rc;
   }
 #ifdef BC_EXPERIMENT
   if (const char* pm = getenv("BC_PIPE")) e->pipe = atoi(pm) != 0;
-#endif
-  // Tables too large for the memory-side cache get the first-occurrence bit map (bc_kernel.h: two-level counting), and,
-  // when the engine owns the table, the dirty-block map behind it (decided here: the plan the kernels read holds its
-  // offset).  BC_NO_BITMAP: A/B builds.
-  e->table_entries = P.sparse ? 0 : e->h.table_entries;
-  P.dirty_off = 0;
-#ifndef BC_NO_BITMAP
-  {
-    uint64_t bitmap_from = 1ull << 26;
-    if (const char* ev = getenv("BC_BITMAP_MIN_ENTRIES")) bitmap_from = strtoull(ev, nullptr, 0);  // tests: small tables too
-    if (!P.sparse && !P.has_random && !e->long_only && e->table_entries >= bitmap_from) {
-      e->n_bit_words = (e->table_entries + 31) / 32;
-      if (!table_mem) {
-        P.dirty_off = (e->n_bit_words + 3) & ~3ull;
-        e->dirty_bytes = (((e->table_entries + 63) / 64) + 15) & ~15ull;
-      }
-    }
-  }
 #endif
   HIP_TRY(hipMalloc((void**)&e->d_plan, sizeof(DevPlan)));
   HIP_TRY(hipMemcpy(e->d_plan, &P, sizeof(DevPlan), hipMemcpyHostToDevice));
@@ -897,522 +848,6 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
   return BC_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Scheme-specialised kernel: the same device code (bc_kernel.h) compiled at run time with the plan
-// as a compile-time constant, so the shift programs, offsets, thresholds and loop bounds of THIS
-// scheme are immediates and fully unrolled.  The generic kernel stays the reference path: if the
-// run-time compiler is unavailable or fails, the engine says so once and keeps using it.
-// ------------------------------------------------------------------------------------------------
-static DevGroup* addr_fields(DevGroup& G, uint64_t* (&f)[kAddrPerGroup]) {
-  uint64_t* fields[kAddrPerGroup] = {&G.dtable_a, &G.r1_a,    &G.r2_a,       &G.rn_a,        &G.rlen_a,
-                                     &G.hkeys_a,  &G.hvals_a, &G.seed_off_a, &G.seed_list_a, &G.odd_list_a,
-                                     &G.tier_off_a, &G.tier_list_a, &G.seed2_off_a, &G.seed2_list_a, &G.tier_bkt_a,
-                                     &G.seed3_off_a, &G.seed3_list_a};
-  for (int k = 0; k < kAddrPerGroup; ++k) f[k] = fields[k];
-  return &G;
-}
-
-// the translation unit of a plan: the plan bytes (table addresses zeroed -- the kernel reads them from
-// bc_jit_addr) plus the kernel entry point
-static std::string jit_source(DevPlan P) {
-  for (int g = 0; g < kMaxGroups; ++g) {
-    uint64_t* f[kAddrPerGroup];
-    addr_fields(P.groups[g], f);
-    for (int k = 0; k < kAddrPerGroup; ++k) *f[k] = 0;
-  }
-  P.lhash_a = 0;
-  std::string src = "#define BC_JIT_TU 1\n#include \"bc_kernel.h\"\n"
-                    "extern \"C\" __constant__ uint64_t bc_jit_addr[" +
-                    std::to_string(kMaxGroups * kAddrPerGroup + kPlanAddrs) +
-                    "] = {};\nnamespace bc {\nstruct PlanBytes { unsigned char b[" + std::to_string(sizeof(DevPlan)) +
-                    "]; };\n__device__ constexpr PlanBytes kPlanBytes = {{";
-  const unsigned char* pb = reinterpret_cast<const unsigned char*>(&P);
-  for (size_t i = 0; i < sizeof(DevPlan); ++i) {
-    src += std::to_string((unsigned)pb[i]);
-    src += (i + 1 < sizeof(DevPlan)) ? "," : "";
-    if ((i & 63) == 63) src += "\n";
-  }
-  src += "}};\n__device__ constexpr DevPlan kPlan = __builtin_bit_cast(DevPlan, kPlanBytes);\n}\n";
-#ifdef BC_PROFILE
-  src += "extern \"C\" __device__ unsigned long long bc_g_profile[16] = {};\n";
-#endif
-  src += "extern \"C\" __global__ __launch_bounds__(BC_TPB, BC_MIN_WAVES) void bc_jit_match_count(\n"
-         "    const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual, const uint16_t* __restrict__ lens,\n"
-         "    const uint16_t* __restrict__ qlens,\n"
-         "    uint32_t stride, uint32_t read_len, uint32_t nd, uint64_t n_reads, uint32_t region, uint32_t* __restrict__ table,\n"
-         "    uint32_t* __restrict__ bits, unsigned long long* __restrict__ slots, uint32_t* __restrict__ vals, uint64_t smask,\n"
-         "    unsigned long long* __restrict__ counters, uint8_t* __restrict__ trace_outcome, uint64_t* __restrict__ trace_idx,\n"
-         "    uint32_t flags, uint32_t* __restrict__ count_log) {\n"
-         "  // the batch shape is part of the specialisation: stride, read length and LDS region are immediates\n"
-         "  bc::match_count_body<JIT_NW, JIT_NWW, JIT_LENS != 0, (JIT_STRIDE % 4) == 0>(bc::kPlan, seq, qual, JIT_LENS ? lens : nullptr,\n"
-         "      JIT_LENS ? qlens : nullptr, JIT_STRIDE,\n"
-         "      JIT_LENS ? read_len : JIT_READ_LEN, ((JIT_LENS ? JIT_STRIDE : JIT_READ_LEN) + 3) / 4,\n"
-         "      n_reads, JIT_REGION, table, bits, slots, vals, smask, counters, JIT_TRACE ? trace_outcome : nullptr,\n"
-         "      JIT_TRACE ? trace_idx : nullptr, flags, count_log);\n}\n";
-  return src;
-}
-
-extern char** environ;
-
-static const char* const kJitHdrNames[] = {"bc_intrin.h", "bc_device_plan.h", "bc_lane.h", "bc_kernel.h"};
-static const char* const kJitHdrText[] = {kJitSrc_bc_intrin_h, kJitSrc_bc_device_plan_h, kJitSrc_bc_lane_h, kJitSrc_bc_kernel_h};
-
-// Waves per SIMD worth asking the register allocator for: as many workgroups as the LDS lets a CU hold (each puts one
-// wave on every SIMD), between 3 and 5 -- a kernel that waits on table lookups (large sets) runs ~10 % faster at 5 than
-// at 4; long reads keep two (their tiles fill the LDS at that occupancy anyway, and 256 VGPRs spare them spills).
-static int jit_first_min_waves(int NW, uint32_t lds_per_wg, uint32_t lds_limit) {
-#ifdef BC_EXPERIMENT
-  if (const char* v = getenv("BC_JIT_MIN_WAVES")) return atoi(v);
-#endif
-  if (NW > 4) return 2;
-  const int by_lds = (int)(lds_limit / (lds_per_wg + 64u));
-  return std::max(3, std::min(5, by_lds));
-}
-
-// scratch bytes per lane a code object's kernel needs, read from its metadata (msgpack key .private_segment_fixed_size);
-// -1 when the key is not found
-static int code_scratch_bytes(const std::vector<char>& code) {
-  static const char kKey[] = ".private_segment_fixed_size";
-  const size_t kl = sizeof(kKey) - 1;
-  if (code.size() < kl + 5) return -1;
-  for (size_t i = 0; i + kl + 5 <= code.size(); ++i) {
-    if (code[i] != '.' || memcmp(&code[i], kKey, kl) != 0) continue;
-    const unsigned char* v = reinterpret_cast<const unsigned char*>(&code[i + kl]);
-    if (v[0] < 0x80) return v[0];
-    if (v[0] == 0xcc) return v[1];
-    if (v[0] == 0xcd) return (v[1] << 8) | v[2];
-    if (v[0] == 0xce) return (int)(((uint32_t)v[1] << 24) | (v[2] << 16) | (v[3] << 8) | v[4]);
-    return -1;
-  }
-  return -1;
-}
-
-// stride / read_len: the batch shape the kernel is specialised for (read_len = 0 with per-read lengths)
-static std::vector<std::string> jit_defines(int NW, int NWW, bool lens, bool tables, bool trace, uint32_t stride, uint32_t read_len,
-                                            uint32_t region, bool conservative, int min_waves) {
-  std::vector<std::string> d = {"-DJIT_NW=" + std::to_string(NW), "-DJIT_NWW=" + std::to_string(NWW),
-                                "-DJIT_STRIDE=" + std::to_string(stride), "-DJIT_READ_LEN=" + std::to_string(lens ? 0u : read_len),
-                                "-DJIT_REGION=" + std::to_string(region),
-                                lens ? "-DJIT_LENS=1" : "-DJIT_LENS=0", tables ? "-DJIT_LHASH=1" : "-DJIT_LHASH=0", trace ? "-DJIT_TRACE=1" : "-DJIT_TRACE=0",
-                                // registers: long reads keep two waves per SIMD resident anyway (their tiles fill the
-                                // LDS), so they may use 256 VGPRs instead of spilling at 168
-                                "-DBC_MIN_WAVES=" + std::to_string(min_waves), "-DBC_TPB=" + std::to_string(kTPB)};
-#ifdef BC_PROFILE
-  d.push_back("-DBC_PROFILE=1");
-#endif
-  if (conservative) d.push_back("-DBC_NO_STATIC_COUNT=1");
-#ifdef BC_VARIANT_FLAGS  // A/B builds (tools/ab.sh): the same -D switches for the specialised kernels
-  {
-    std::string t;
-    for (const char* c = BC_VARIANT_FLAGS;; ++c) {
-      if (*c == ' ' || *c == 0) {
-        if (!t.empty()) d.push_back(t);
-        t.clear();
-        if (*c == 0) break;
-      } else {
-        t += *c;
-      }
-    }
-  }
-#endif
-#ifdef BC_EXPERIMENT
-  d.push_back("-DBC_EXPERIMENT=1");
-  if (const char* extra = getenv("BC_JIT_FLAGS")) {  // experiments: extra compiler flags, space separated
-    std::string t;
-    for (const char* c = extra;; ++c) {
-      if (*c == ' ' || *c == ';' || *c == 0) {
-        if (!t.empty()) d.push_back(t);
-        t.clear();
-        if (*c == 0) break;
-      } else {
-        t += *c;
-      }
-    }
-  }
-#endif
-  return d;
-}
-
-static uint64_t fnv1a(const std::string& s, uint64_t h = 0xcbf29ce484222325ull) {
-  for (unsigned char c : s) h = (h ^ c) * 0x100000001b3ull;
-  return h;
-}
-
-static bool read_file(const std::string& path, std::vector<char>& out) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  out.resize(n > 0 ? (size_t)n : 0);
-  const bool ok = n > 0 && fread(out.data(), 1, (size_t)n, f) == (size_t)n;
-  fclose(f);
-  return ok;
-}
-
-static bool write_file(const std::string& path, const void* data, size_t n) {
-  const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f) return false;
-  const bool ok = fwrite(data, 1, n, f) == n;
-  fclose(f);
-  if (!ok || rename(tmp.c_str(), path.c_str()) != 0) {
-    remove(tmp.c_str());
-    return false;
-  }
-  return true;
-}
-
-// directory of code objects shipped next to the library (filled by `make jit_cache` / build())
-static std::string lib_cache_dir() {
-  Dl_info info;
-  if (!dladdr((const void*)&fnv1a, &info) || !info.dli_fname) return "";
-  std::string p = info.dli_fname;
-  const size_t k = p.rfind('/');
-  return (k == std::string::npos ? std::string(".") : p.substr(0, k)) + "/jit_cache";
-}
-
-// in-process compile (hiprtc)
-static bool jit_compile_rtc(const std::string& src, const std::string& arch, const std::vector<std::string>& defs,
-                            std::vector<char>& code, std::string& log) {
-  hiprtcProgram prog = nullptr;
-  if (hiprtcCreateProgram(&prog, src.c_str(), "bc_jit.hip", 4, const_cast<const char**>(kJitHdrText),
-                          const_cast<const char**>(kJitHdrNames)) != HIPRTC_SUCCESS) {
-    log = "hiprtcCreateProgram failed";
-    return false;
-  }
-  const std::string a = "--offload-arch=" + arch;
-  std::vector<const char*> opts = {a.c_str(), "-O3", "-std=c++17"};
-  for (const auto& d : defs) opts.push_back(d.c_str());
-  const hiprtcResult cr = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
-  size_t ls = 0;
-  hiprtcGetProgramLogSize(prog, &ls);
-  log.assign(ls, 0);
-  if (ls) hiprtcGetProgramLog(prog, &log[0]);
-  if (cr != HIPRTC_SUCCESS) {
-    log = std::string(hiprtcGetErrorString(cr)) + "\n" + log;
-    hiprtcDestroyProgram(&prog);
-    return false;
-  }
-  size_t cs = 0;
-  hiprtcGetCodeSize(prog, &cs);
-  code.resize(cs);
-  hiprtcGetCode(prog, code.data());
-  hiprtcDestroyProgram(&prog);
-  return true;
-}
-
-// the ROCm compiler driver as a child process: the same compiler the library itself was built with
-// (an in-process hiprtc may resolve to whatever copy the host application bundles)
-static bool jit_compile_driver(const std::string& driver, const std::string& dir, const std::string& stem,
-                               const std::string& src, const std::string& arch, const std::vector<std::string>& defs,
-                               std::vector<char>& code, std::string& log) {
-  for (int i = 0; i < 4; ++i)
-    if (!write_file(dir + "/" + kJitHdrNames[i], kJitHdrText[i], strlen(kJitHdrText[i]))) return false;
-  // several ranks may compile the same kernel at once: every process works on its own files
-  const std::string mine = dir + "/" + stem + "." + std::to_string((long)getpid());
-  const std::string in = mine + ".hip", out = mine + ".co.part", err = mine + ".log";
-  if (!write_file(in, src.data(), src.size())) return false;
-  // argument vector, no shell: paths may hold any character
-  std::vector<std::string> argv_s = {driver, "--genco", "--offload-arch=" + arch, "-O3", "-std=c++17", "-I" + dir};
-  for (const auto& d : defs) argv_s.push_back(d);
-  argv_s.insert(argv_s.end(), {"-o", out, in});
-  std::vector<char*> argv;
-  for (auto& a : argv_s) argv.push_back(const_cast<char*>(a.c_str()));
-  argv.push_back(nullptr);
-  posix_spawn_file_actions_t fa;
-  posix_spawn_file_actions_init(&fa);
-  posix_spawn_file_actions_addopen(&fa, 1, err.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  posix_spawn_file_actions_adddup2(&fa, 1, 2);
-  // the compiler child gets the caller's environment minus what would drag a tool of the parent into it: preload
-  // hooks (a profiler's), the profiler's own variables, and this engine's switches
-  std::vector<char*> envp;
-  for (char** ev = environ; ev && *ev; ++ev) {
-    static const char* const kDrop[] = {"LD_PRELOAD=", "ROCP", "ROCPROF", "HSA_TOOLS", "ROCTX", "BC_", "HIP_LAUNCH_BLOCKING="};
-    bool drop = false;
-    for (const char* d : kDrop) drop = drop || strncmp(*ev, d, strlen(d)) == 0;
-    if (!drop) envp.push_back(*ev);
-  }
-  envp.push_back(nullptr);
-  pid_t pid = 0;
-  int rc = posix_spawn(&pid, driver.c_str(), &fa, nullptr, argv.data(), envp.data());
-  posix_spawn_file_actions_destroy(&fa);
-  if (rc == 0) {
-    int status = 0;
-    while (waitpid(pid, &status, 0) < 0 && errno == EINTR) {
-    }
-    rc = (WIFEXITED(status) && WEXITSTATUS(status) == 0) ? 0 : 1;
-  }
-  std::vector<char> lg;
-  if (read_file(err, lg)) log.assign(lg.begin(), lg.end());
-  const bool ok = rc == 0 && read_file(out, code);
-  remove(out.c_str());
-  remove(err.c_str());
-  if (ok) remove(in.c_str());
-  return ok;
-}
-
-// Code object of the plan's specialised kernel: from a cache directory when it was built before
-// (next to the library, or $BC_JIT_CACHE), else compiled now and stored where that is possible.
-struct JitShape {
-  int NW, NWW;  // exact words per read / words of candidate offsets of the batch shape
-  bool lens, tables, trace;
-  uint32_t stride, read_len, region;
-  bool conservative = false;  // last try after builds that needed scratch memory: the loop-based counting form
-  int min_waves = 3;          // waves per SIMD the register allocation must leave room for (__launch_bounds__)
-};
-
-// the generic kernel instantiation a read length falls into: 32-base words per read (4 / 8 / 10)
-static int generic_nw(uint32_t maxlen) { return maxlen <= 128 ? 4 : (maxlen <= 256 ? 8 : 10); }
-// per-wave LDS region: 64 reads + the few bytes past them the lane code may touch
-static uint32_t tile_alloc_for(uint32_t L, uint32_t stride, int nw_generic) {
-  const uint32_t slack = (uint32_t)nw_generic * 32u + 16u + (L > stride ? L - stride : 0u);
-  return (64u * stride + slack + 15u) & ~15u;
-}
-static uint32_t lds_tiles_for(const DevPlan& P, uint32_t stride, int nw_generic, bool pipe) {
-  return tile_alloc_for(P.L, stride, nw_generic) * (kTPB / 64) * ((P.quality_on && pipe) ? 2u : 1u) +
-         (P.defer_search() ? (kTPB / 64) * kQueueBytes : 0u);  // + the waves' search queues (bc_kernel.h)
-}
-// The LDS exact-match tables pay for their LDS (fewer resident workgroups) as long as at least two workgroups stay
-// resident per CU (long reads: the tiles alone take half the LDS)
-static bool jit_tables_fit(const DevPlan& P, uint32_t stride, int nw_generic, uint32_t lds_limit, bool pipe = true) {
-  const uint32_t lds_tables = P.lhash_vec * 16u;
-  return lds_tables != 0 && 2u * (lds_tiles_for(P, stride, nw_generic, pipe) + lds_tables + 64u) <= lds_limit;
-}
-
-static bool jit_get_code(const DevPlan& P, const std::string& arch, const JitShape& sh, bool may_compile,
-                         const char* store_dir, std::vector<char>& code, std::string& log) {
-  const std::string src = jit_source(P);
-  const std::vector<std::string> defs = jit_defines(sh.NW, sh.NWW, sh.lens, sh.tables, sh.trace, sh.stride, sh.read_len, sh.region, sh.conservative, sh.min_waves);
-  std::string key = arch + "\n" + src;
-  for (const auto& d : defs) key += d;
-  for (int i = 0; i < 4; ++i) key += kJitHdrText[i];
-  char name[64];
-  snprintf(name, sizeof name, "bcjit_%016llx", (unsigned long long)fnv1a(key));
-  if (const char* src_out = getenv("BC_JIT_SRC")) write_file(src_out, src.data(), src.size());  // debugging
-  std::vector<std::string> dirs;
-  if (store_dir) dirs.push_back(store_dir);
-  if (const char* c = getenv("BC_JIT_CACHE")) dirs.push_back(c);
-  dirs.push_back(lib_cache_dir());
-  const char* drv = getenv("BC_JIT_COMPILER");  // "rtc" forces the in-process compiler
-  const std::string driver = drv ? drv : "/opt/rocm/bin/hipcc";
-  const bool have_driver = driver != "rtc" && access(driver.c_str(), X_OK) == 0;
-  // objects built by the in-process compiler are kept apart (<name>_rtc.co): which compiler that is depends on
-  // the host application, and its code may be much worse than the driver's
-  for (const auto& d : dirs)
-    if (!d.empty() && read_file(d + "/" + name + ".co", code)) return true;
-  if (!have_driver)
-    for (const auto& d : dirs)
-      if (!d.empty() && read_file(d + "/" + name + "_rtc.co", code)) return true;
-  if (!may_compile) {
-    log = "not in the kernel cache";
-    return false;
-  }
-  // where the result (and the driver's scratch files) can go
-  std::string wdir;
-  for (const auto& d : dirs) {
-    if (d.empty()) continue;
-    mkdir(d.c_str(), 0755);
-    if (access(d.c_str(), W_OK) == 0) {
-      wdir = d;
-      break;
-    }
-  }
-  if (wdir.empty()) {
-    const char* t = getenv("TMPDIR");
-    wdir = std::string(t && *t ? t : "/tmp") + "/barcode-count-jit-" + std::to_string((long)getuid());
-    mkdir(wdir.c_str(), 0700);
-    if (access(wdir.c_str(), W_OK) != 0) wdir.clear();
-  }
-  bool ok = false, by_driver = false;
-  if (have_driver && !wdir.empty()) ok = by_driver = jit_compile_driver(driver, wdir, name, src, arch, defs, code, log);
-  if (!ok) ok = jit_compile_rtc(src, arch, defs, code, log);
-  if (ok && !wdir.empty()) write_file(wdir + "/" + name + (by_driver ? ".co" : "_rtc.co"), code.data(), code.size());
-  return ok;
-}
-
-// The code object to use for a shape: the build with the most waves per SIMD that keeps everything in registers, then
-// the loop-based counting form at three and, last, two waves; all of them come from / go to the cache, so a later run pays file reads
-// only.  first_mw: jit_first_min_waves().
-static bool jit_pick_code(const DevPlan& P, const std::string& arch, JitShape sh, int first_mw, bool may_compile,
-                          const char* store_dir, std::vector<char>& code, std::string& log) {
-  const int floor_mw = std::min(first_mw, sh.NW > 4 ? 2 : 3);
-  for (int pass = 0; pass < 2; ++pass) {
-    sh.conservative = pass == 1;
-    for (int mw = pass == 0 ? first_mw : floor_mw; mw >= (pass == 0 ? floor_mw : 2); --mw) {
-      sh.min_waves = mw;
-      if (!jit_get_code(P, arch, sh, may_compile, store_dir, code, log)) return false;  // not cached / did not compile
-      const int scratch = code_scratch_bytes(code);
-      if (scratch == 0) return true;
-#ifdef BC_EXPERIMENT
-      if (getenv("BC_JIT_ALLOW_SCRATCH")) return true;
-#endif
-      log = "the build for " + std::to_string(mw) + " waves per SIMD needs " + std::to_string(scratch) + " bytes of scratch memory per lane";
-    }
-  }
-  code.clear();
-  return false;
-}
-
-static std::string jit_arch(int device) {
-  hipDeviceProp_t prop;
-  std::string arch = "gfx950";
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.gcnArchName[0]) arch = prop.gcnArchName;
-  // the cache is keyed by the bare target name; target features (sramecc, xnack) keep their defaults
-  const size_t colon = arch.find(':');
-  if (colon != std::string::npos) arch.resize(colon);
-  return arch;
-}
-
-// code object -> module on this engine's device, table addresses filled in
-static bool jit_load(bc_engine* e, bc_engine::Jit& out) {
-  if (const char* dump = getenv("BC_JIT_DUMP")) write_file(dump, out.code.data(), out.code.size());
-  hipDeviceptr_t addr = nullptr;
-  size_t addr_bytes = 0;
-  if (hipModuleLoadData(&out.mod, out.code.data()) != hipSuccess ||
-      hipModuleGetFunction(&out.fn, out.mod, "bc_jit_match_count") != hipSuccess ||
-      hipModuleGetGlobal(&addr, &addr_bytes, out.mod, "bc_jit_addr") != hipSuccess ||
-      addr_bytes != (kMaxGroups * kAddrPerGroup + kPlanAddrs) * sizeof(uint64_t)) {
-    fprintf(stderr, "[barcode-count] scheme-specialised kernel did not load; using the generic kernel\n");
-    out.fn = nullptr;
-    return false;
-  }
-  // A build whose registers ended up in scratch memory (seen with the comgr that PyTorch bundles, reached through an
-  // in-process hiprtc) is slower than the generic kernel: do not use it.
-  int scratch = 0;
-  bool allow_scratch = false;
-#ifdef BC_EXPERIMENT
-  allow_scratch = getenv("BC_JIT_ALLOW_SCRATCH") != nullptr;
-#endif
-  if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, out.fn) == hipSuccess && scratch > 0 && !allow_scratch) {
-    fprintf(stderr, "[barcode-count] scheme-specialised kernel build uses %d bytes of scratch memory per lane: not used\n", scratch);
-    (void)hipModuleUnload(out.mod);
-    out.mod = nullptr;
-    out.fn = nullptr;
-    out.scratch = true;
-    return false;
-  }
-  // the table addresses of THIS engine
-  std::vector<uint64_t> table(kMaxGroups * kAddrPerGroup + kPlanAddrs, 0);
-  for (int g = 0; g < kMaxGroups; ++g) {
-    uint64_t* f[kAddrPerGroup];
-    addr_fields(e->h.plan.groups[g], f);
-    for (int k = 0; k < kAddrPerGroup; ++k) table[g * kAddrPerGroup + k] = *f[k];
-  }
-  table[kMaxGroups * kAddrPerGroup] = e->h.plan.lhash_a;
-  if (hipMemcpyHtoD(addr, table.data(), table.size() * sizeof(uint64_t)) != hipSuccess) {
-    out.fn = nullptr;
-    return false;
-  }
-  std::vector<char>().swap(out.code);
-  return true;
-}
-
-// The specialised kernel of one shape, if it can be had now.  Never blocks in the default mode: a
-// cache hit loads at once; a miss is compiled by a worker thread once the run has proved long enough
-// to pay for it, and picked up by a later launch.  Returns nullptr while the generic kernel must do.
-static hipFunction_t jit_function(bc_engine* e, uint64_t key, const JitShape& sh, uint32_t lds_jit, int* per_cu) {
-  const int first_mw = jit_first_min_waves(sh.NW, lds_jit, e->lds_limit);
-  auto& slot = e->jit[key];
-  if (!slot) slot.reset(new bc_engine::Jit());
-  bc_engine::Jit& j = *slot;
-  typedef bc_engine::Jit J;
-  if (j.state.load(std::memory_order_acquire) == J::kIdle) {
-    const std::string arch = jit_arch(e->device);
-    if (jit_pick_code(e->h.plan, arch, sh, first_mw, false, nullptr, j.code, j.log)) {
-      j.state.store(J::kCodeReady, std::memory_order_release);
-    } else if (e->jit_mode == 2) {
-      const bool ok = jit_pick_code(e->h.plan, arch, sh, first_mw, true, nullptr, j.code, j.log);
-      if (!ok)
-        fprintf(stderr, "[barcode-count] scheme-specialised kernel did not compile; using the generic kernel\n%.2000s\n",
-                j.log.c_str());
-      j.state.store(ok ? J::kCodeReady : J::kFailed, std::memory_order_release);
-    } else if (e->jit_mode == 1) {
-      if (e->reads_seen < (1ull << 20)) return nullptr;  // ask again when the run has grown
-      j.state.store(J::kCompiling, std::memory_order_release);
-      const DevPlan plan = e->h.plan;  // the worker's own copy
-      bc_engine::Jit* jp = &j;
-      const JitShape shape = sh;
-      j.worker = std::thread([jp, plan, arch, shape, first_mw]() {
-        const bool ok = jit_pick_code(plan, arch, shape, first_mw, true, nullptr, jp->code, jp->log);
-        jp->state.store(ok ? J::kCodeReady : J::kFailed, std::memory_order_release);
-      });
-    } else {
-      j.state.store(J::kFailed, std::memory_order_release);  // cache hits only
-    }
-  }
-  if (j.state.load(std::memory_order_acquire) == J::kCodeReady) {
-    if (j.worker.joinable()) j.worker.join();
-    bool ok = jit_load(e, j);
-    if (!ok) fprintf(stderr, "[barcode-count] using the generic kernel\n");
-    if (ok && (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&j.per_cu, j.fn, kTPB, lds_jit) != hipSuccess || j.per_cu < 1))
-      j.per_cu = 1;
-    j.state.store(ok ? J::kLoaded : J::kFailed, std::memory_order_release);
-  }
-  if (j.state.load(std::memory_order_acquire) == J::kFailed && j.worker.joinable()) {
-    j.worker.join();
-    fprintf(stderr, "[barcode-count] scheme-specialised kernel did not compile; using the generic kernel\n%.2000s\n",
-            j.log.c_str());
-  }
-  if (j.state.load(std::memory_order_acquire) != J::kLoaded) return nullptr;
-  *per_cu = j.per_cu;
-  return j.fn;
-}
-
-// build-time hook (not part of the documented ABI): compiles the specialised kernel of a plan for
-// gfx950 without touching a device, stores it in cache_dir (NULL: next to the library) and
-// optionally also writes it to out_path
-extern "C" int bc_internal_jit_compile(const bc_plan* p, uint32_t stride, uint32_t read_len, int lens, const char* cache_dir,
-                                       const char* out_path) {
-  HostDevPlan h;
-  if (!p->lower(h)) return BC_ERR_UNSUPPORTED;
-#ifdef BC_EXPERIMENT
-  if (const char* lh = getenv("BC_LHASH")) {
-    if (atoi(lh) == 0) {
-      h.plan.lhash_vec = 0;
-      for (uint32_t g = 0; g < h.plan.n_groups; ++g) h.plan.groups[g].lhash_nb = 0;
-    }
-  }
-  if (const char* ab = getenv("BC_ABLATE")) h.plan.ablate = (uint32_t)strtoul(ab, nullptr, 0);
-#endif
-  // the dirty-block map's offset is part of the plan a kernel is specialised for: decide it as engine_init does for an
-  // engine-owned table (default threshold)
-  h.plan.dirty_off = 0;
-#ifndef BC_NO_BITMAP
-  {
-    uint64_t bitmap_from = 1ull << 26;
-    if (const char* ev = getenv("BC_BITMAP_MIN_ENTRIES")) bitmap_from = strtoull(ev, nullptr, 0);
-    if (!h.plan.sparse && !h.plan.has_random && h.table_entries >= bitmap_from) h.plan.dirty_off = (((h.table_entries + 31) / 32) + 3) & ~3ull;
-  }
-#endif
-  std::vector<char> code;
-  std::string log;
-  const std::string dir = cache_dir ? cache_dir : lib_cache_dir();
-  const uint32_t maxlen = lens ? stride : read_len;
-  if (maxlen == 0 || maxlen > stride || maxlen > 256) {
-    set_error("bc_plan_precompile: read_len must be in 1..stride and at most 256 bases for a specialised kernel");
-    return BC_ERR_INVALID;
-  }
-  JitShape sh;
-  sh.NW = (int)((maxlen + 31) / 32);
-  sh.NWW = maxlen >= h.plan.L ? (int)((maxlen - h.plan.L + 1 + 31) / 32) : 1;
-  sh.lens = lens != 0;
-  sh.trace = false;
-  sh.stride = stride;
-  sh.read_len = read_len;
-  sh.region = tile_alloc_for(h.plan.L, stride, generic_nw(maxlen));
-  sh.tables = jit_tables_fit(h.plan, stride, generic_nw(maxlen), 160u * 1024u);
-  uint32_t lds_wg = lds_tiles_for(h.plan, stride, generic_nw(maxlen), true) + (sh.tables ? h.plan.lhash_vec * 16u : 0u);
-  if (!h.plan.sparse && !h.plan.has_random && h.table_entries <= 0xFFFFFFFFull && 2u * (lds_wg + kHotBytes + 64u) <= 160u * 1024u)
-    lds_wg += kHotBytes;  // the hot-counter cache, as launch_match decides it
-  if (!jit_pick_code(h.plan, "gfx950", sh, jit_first_min_waves(sh.NW, lds_wg, 160u * 1024u), true, dir.c_str(), code, log)) {
-    set_error("scheme-specialised kernel did not compile: " + log);
-    return BC_ERR_INVALID;
-  }
-  if (out_path) write_file(out_path, code.data(), code.size());
-  return BC_OK;
-}
-
 #ifdef BC_PROFILE
 extern "C" __device__ unsigned long long bc_g_profile[16] = {};
 // perf experiments (BC_PROFILE builds only): sums the tick counters of the generic and specialised kernels
@@ -1421,7 +856,7 @@ extern "C" int bc_internal_profile_read(bc_engine* e, unsigned long long* out) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpyFromSymbol(a, HIP_SYMBOL(bc_g_profile), sizeof(a)));
   for (int k = 0; k < 16; ++k) out[k] = a[k];
-  for (auto& kv : e->jit) {
+  for (auto& kv : e->jit.slots) {
     if (!kv.second->fn) continue;
     hipDeviceptr_t p = nullptr;
     size_t sz = 0;
@@ -1473,43 +908,24 @@ static int fold_log(bc_engine* e, uint64_t n) {
   return BC_OK;
 }
 
+// s: match_shape() of the batch; NW = s.generic_nw
 template <int NW, int NWW>
 static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
-                        uint32_t read_len, uint32_t nd, uint64_t n_reads, uint64_t trace_off, int nw_exact, int nww_exact) {
-  const uint32_t tile_alloc = tile_alloc_for(e->h.plan.L, stride, NW);
-  // [exact-match tables][per wave: sequence region (+ quality region when the fetch is pipelined)]
-  // The tables pay for their LDS (fewer resident workgroups) in the specialised kernel, which is short on
-  // instructions but long on gather latency; the generic kernel keeps its occupancy instead.
-  const uint32_t lds_tiles = lds_tiles_for(e->h.plan, stride, NW, e->pipe);
-  const uint32_t lds_tables = e->h.plan.lhash_vec * 16u;
-  const bool tables_fit = jit_tables_fit(e->h.plan, stride, NW, e->lds_limit, e->pipe);
-  const bool tables_generic = e->lhash_mode >= 2 && tables_fit;
-  const bool tables_jit = e->lhash_mode >= 1 && tables_fit;
-  // the hot-counter cache (bc_kernel.h): dense tables indexed by 32 bits, where its 8 KiB leave the resident
-  // workgroups as they are (two per CU at the least)
-#ifdef BC_NO_HOT  // A/B builds
-  const bool hot_ok = false;
-#else
-  const bool hot_ok = !e->h.plan.sparse && !e->h.plan.has_random && e->table_entries != 0 && e->table_entries <= 0xFFFFFFFFull;
-#endif
-  const bool hot_generic = hot_ok && 2u * (lds_tiles + (tables_generic ? lds_tables : 0u) + kHotBytes + 64u) <= e->lds_limit;
-  const bool hot_jit = hot_ok && 2u * (lds_tiles + (tables_jit ? lds_tables : 0u) + kHotBytes + 64u) <= e->lds_limit;
+                        uint32_t read_len, uint32_t nd, uint64_t n_reads, uint64_t trace_off, const MatchShape& s) {
   // log mode (bc_fold.h): the batch goes through in chunks of at most log_chunk reads, each matched into the log and
   // folded before the next one overwrites it.  (The hot-counter cache keeps its LDS either way: the same code object.)
   const bool use_log = log_mode_for(e, n_reads);
   const bool hot_on = !use_log || e->log_hot;
-  const uint32_t flags = (e->pipe ? 1u : 0u) | (tables_generic ? 2u : 0u) | (hot_generic && hot_on ? 4u : 0u);
-  const uint32_t lds = lds_tiles + (tables_generic ? lds_tables : 0u) + (hot_generic ? kHotBytes : 0u);
-  const uint32_t lds_jit = lds_tiles + (tables_jit ? lds_tables : 0u) + (hot_jit ? kHotBytes : 0u);  // (a function of the plan and stride class)
-  if (lds + 64 > e->lds_limit) {
+  const uint32_t flags = (e->pipe ? 1u : 0u) | (s.tables_generic ? 2u : 0u) | (s.hot_generic && hot_on ? 4u : 0u);
+  if (s.lds + 64 > e->lds_limit) {
     set_error("read stride too large for one LDS tile");
     return BC_ERR_UNSUPPORTED;
   }
   auto kern = match_count_kernel<NW, NWW>;
-  if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (s.lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
   // persistent grid: as many workgroups as the chip holds at once (or fewer for a small batch)
   int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kTPB, lds));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kTPB, s.lds));
   if (per_cu < 1) per_cu = 1;
   const uint64_t resident = (uint64_t)per_cu * e->n_cus;
   const uint64_t blocks = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, resident);
@@ -1523,23 +939,8 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   hipFunction_t jit_fn = nullptr;
   e->reads_seen += n_reads;
   if (NW <= 8 && NWW <= 4 && e->jit_mode != 0) {  // reads up to 256 bases; longer ones stay on the generic kernel
-    const bool tracing = e->trace_outcome != nullptr;
-    const bool tables = tables_jit && lds_tables != 0;
-    // the specialised kernel is compiled for the exact shape of this batch (e.g. <5,3> for 150-base reads with a
-    // 59-base scheme), not for the next generic instantiation up (<8,4>)
-    // ... and for its stride and (fixed) read length, so that every offset, loop bound and wait count is an immediate
-    JitShape sh;
-    sh.NW = nw_exact;
-    sh.NWW = nww_exact;
-    sh.lens = d_lens != nullptr;
-    sh.tables = tables;
-    sh.trace = tracing;
-    sh.stride = stride;
-    sh.read_len = sh.lens ? 0u : read_len;
-    sh.region = tile_alloc;
-    const uint64_t jit_key = ((uint64_t)stride << 32) | ((uint64_t)sh.read_len << 16) | (uint64_t)(((nw_exact * 16 + nww_exact) * 2 + (d_lens ? 1 : 0)) * 4 + (tables ? 2 : 0) + (tracing ? 1 : 0));
     int per_cu_jit = 1;
-    jit_fn = jit_function(e, jit_key, sh, lds_jit, &per_cu_jit);
+    jit_fn = e->jit.function(e->h.plan, e->device, e->jit_mode, e->reads_seen, s, &per_cu_jit);
     if (jit_fn) blocks_jit = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, (uint64_t)per_cu_jit * e->n_cus);
   }
   if (use_log) {
@@ -1558,17 +959,17 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     uint32_t* a_log = use_log ? e->d_log : nullptr;
     uint64_t a_n = n_c;
     if (jit_fn) {
-      uint32_t a_region = tile_alloc;
+      uint32_t a_region = s.region;
       uint64_t a_smask = e->n_slots ? e->n_slots - 1 : 0;
-      uint32_t a_flags = (e->pipe ? 1u : 0u) | (tables_jit ? 2u : 0u) | (hot_jit && hot_on ? 4u : 0u);
+      uint32_t a_flags = (e->pipe ? 1u : 0u) | (s.tables_jit ? 2u : 0u) | (s.hot_jit && hot_on ? 4u : 0u);
       void* args[] = {&a_seq, &a_qual, &a_lens, &a_qlens, &stride, &read_len, &nd, &a_n, &a_region, &e->d_table, &e->d_bits, &e->d_slots,
                       &e->d_vals, &a_smask, &e->d_counters, &a_to, &a_ti, &a_flags, &a_log};
       const uint64_t grid = std::min<uint64_t>(blocks_jit, (n_c + kTPB - 1) / kTPB);
-      HIP_TRY(hipModuleLaunchKernel(jit_fn, (uint32_t)grid, 1, 1, kTPB, 1, 1, lds_jit, e->stream, args, nullptr));
+      HIP_TRY(hipModuleLaunchKernel(jit_fn, (uint32_t)grid, 1, 1, kTPB, 1, 1, s.lds_jit, e->stream, args, nullptr));
     } else {
       const uint64_t grid = std::min<uint64_t>(blocks, (n_c + kTPB - 1) / kTPB);
-      hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual, a_lens, a_qlens, stride, read_len,
-                         nd, a_n, tile_alloc, e->d_table, e->d_bits, e->d_slots, e->d_vals, e->n_slots ? e->n_slots - 1 : 0, e->d_counters,
+      hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(kTPB), s.lds, e->stream, e->d_plan, a_seq, a_qual, a_lens, a_qlens, stride, read_len,
+                         nd, a_n, s.region, e->d_table, e->d_bits, e->d_slots, e->d_vals, e->n_slots ? e->n_slots - 1 : 0, e->d_counters,
                          a_to, a_ti, flags, a_log);
     }
     HIP_TRY(hipGetLastError());
@@ -1582,7 +983,7 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     e->reads_since_fold += n_reads;
   }
   e->last_kernel = std::string(jit_fn ? "bc_jit_match_count<" : "match_count_kernel<") +
-                   std::to_string(jit_fn ? nw_exact : NW) + "," + std::to_string(jit_fn ? nww_exact : NWW) + ">";
+                   std::to_string(jit_fn ? s.jit.NW : NW) + "," + std::to_string(jit_fn ? s.jit.NWW : NWW) + ">";
   if (e->timing) {
     HIP_TRY(hipEventRecord(e1, e->stream));
     e->events.emplace_back(e0, e1);
@@ -1719,29 +1120,24 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
   }
   // plans or reads beyond the lane-per-read kernel's widths: the wave-per-read kernel (bc_long.h)
   if (e->long_only || maxlen > 320u) return launch_long(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads, trace_off);
-  // candidate offsets 0 .. maxlen-L: how many 32-bit words the anchor / repair vectors need
-  const uint32_t L = e->h.plan.L;
-  const uint32_t nww = maxlen >= L ? (maxlen - L + 1 + 31) / 32 : 1;
-  const int nw_exact = (int)((maxlen + 31) / 32), nww_exact = (int)nww;
+  const MatchShape s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr,
+                                   e->lds_limit, e->pipe, e->lhash_mode);
+  const int nww = s.jit.NWW;  // words of candidate offsets: the exact count; the instantiations round it up
 #define BC_LAUNCH(NW_, NWW_) \
-  return launch_match<NW_, NWW_>(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, nd, n_reads, trace_off, nw_exact, nww_exact)
-  if (maxlen <= 128) {
+  return launch_match<NW_, NWW_>(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, nd, n_reads, trace_off, s)
+  if (s.generic_nw == 4) {
     if (nww <= 1) BC_LAUNCH(4, 1);
     if (nww <= 2) BC_LAUNCH(4, 2);
     BC_LAUNCH(4, 4);
   }
-  if (maxlen <= 256) {
+  if (s.generic_nw == 8) {
     if (nww <= 2) BC_LAUNCH(8, 2);
     if (nww <= 4) BC_LAUNCH(8, 4);
     BC_LAUNCH(8, 8);
   }
-  if (maxlen <= 320) {
-    if (nww <= 4) BC_LAUNCH(10, 4);
-    BC_LAUNCH(10, 10);
-  }
+  if (nww <= 4) BC_LAUNCH(10, 4);  // (up to 320 bases: longer reads went to the wave-per-read kernel)
+  BC_LAUNCH(10, 10);
 #undef BC_LAUNCH
-  set_error("submit: reads longer than 320 bases are not supported");
-  return BC_ERR_UNSUPPORTED;
 }
 
 extern "C" {
@@ -2665,14 +2061,6 @@ int bc_engine_sclk_mhz(bc_engine* e, double* mhz) {
   (void)hipFree(d);
   if (h[1]) *mhz = 100.0 * (double)h[0] / (double)h[1];
   return BC_OK;
-}
-
-int bc_plan_precompile(const bc_plan* p, uint32_t stride, uint32_t read_len, int with_lens, const char* cache_dir) {
-  if (!p) {
-    set_error("bc_plan_precompile: null plan");
-    return BC_ERR_INVALID;
-  }
-  return bc_internal_jit_compile(p, stride, read_len, with_lens, cache_dir, nullptr);
 }
 
 // resolves the recorded event pairs into per-launch times (the stream has drained)

@@ -1,0 +1,79 @@
+// bc_jit.h -- the scheme-specialised match kernel (bc_jit.hip): which kernel shape a batch needs, the plan edits both
+// the engine and the ahead-of-time build apply, and the compiled, cached and loaded kernels of one engine.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+#include <map>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "bc_plan.hpp"
+
+namespace bc {
+
+// The env-driven edits of a freshly lowered plan (BC_ABLATE, BC_LHASH in experiment builds) and the bit-map layout:
+// tables too large for the memory-side cache get the first-occurrence bit map (bc_kernel.h: two-level counting), and,
+// when the engine owns the table, the dirty-block map behind it (the plan the kernels read holds its offset, dirty_off).
+struct PlanSetup {
+  int lhash_mode = 1;        // LDS exact-match tables: 0 never, 1 in the specialised kernel, 2 in both (BC_LHASH=0|1|2)
+  uint64_t n_bit_words = 0;  // words of the bit map (0: none)
+  uint64_t dirty_bytes = 0;  // bytes of the dirty-block map: one flag per 64 entries (0: none)
+};
+PlanSetup plan_setup(HostDevPlan& h, bool long_only, bool own_table);
+
+// the generic kernel instantiation a read length falls into: 32-base words per read (4 / 8 / 10)
+inline int generic_nw(uint32_t maxlen) { return maxlen <= 128 ? 4 : (maxlen <= 256 ? 8 : 10); }
+
+// The specialised kernel's compile-time shape
+struct JitShape {
+  int NW, NWW;  // exact words per read / words of candidate offsets of the batch shape
+  bool lens, tables, trace;
+  uint32_t stride, read_len, region;
+  bool conservative = false;  // last try after builds that needed scratch memory: the loop-based counting form
+  int min_waves = 3;          // waves per SIMD the register allocation must leave room for (__launch_bounds__)
+};
+
+// What a match launch derives from the plan and the batch shape, for the generic kernel and the specialised one
+struct MatchShape {
+  int generic_nw;                   // the generic instantiation's NW
+  uint32_t region;                  // per-wave LDS region: 64 reads + the few bytes past them the lane code may touch
+  uint32_t lds, lds_jit;            // dynamic LDS of the generic / specialised kernel
+  bool tables_generic, tables_jit;  // LDS exact-match tables
+  bool hot_generic, hot_jit;        // hot-counter cache (its LDS; log mode may still switch it off per launch)
+  JitShape jit;
+  int first_min_waves;              // waves per SIMD the specialised build tries first
+  uint64_t key;                     // the engine's key for the specialised kernel of this shape
+};
+// table_entries: 0 for sparse plans; read_len: ignored with per-read lengths (lens); trace: per-read outcomes recorded
+MatchShape match_shape(const DevPlan& P, uint64_t table_entries, uint32_t stride, uint32_t read_len, bool lens, bool trace,
+                       uint32_t lds_limit, bool pipe, int lhash_mode);
+
+// scheme-specialised kernels of one engine, one per MatchShape::key; destruction joins the workers and unloads the
+// modules
+struct JitKernels {
+  struct Jit {
+    enum { kIdle = 0, kCompiling = 1, kCodeReady = 2, kLoaded = 3, kFailed = -1 };
+    std::atomic<int> state{kIdle};
+    std::thread worker;      // compiles in the background while the generic kernel keeps counting
+    std::vector<char> code;  // written by the worker before it publishes kCodeReady
+    std::string log;
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    int per_cu = 0;
+  };
+  std::map<uint64_t, std::unique_ptr<Jit>> slots;
+
+  JitKernels() = default;
+  JitKernels(const JitKernels&) = delete;
+  JitKernels& operator=(const JitKernels&) = delete;
+  ~JitKernels();
+  // The specialised kernel of one shape, if it can be had now (mode: BC_JIT as bc_engine::jit_mode reads it;
+  // reads_seen: reads submitted so far).  Returns nullptr while the generic kernel must do.
+  hipFunction_t function(const DevPlan& plan, int device, int mode, uint64_t reads_seen, const MatchShape& s, int* per_cu);
+};
+
+}  // namespace bc

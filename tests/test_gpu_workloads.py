@@ -321,6 +321,50 @@ def test_specialised_kernel_takes_over_in_the_background(monkeypatch, tmp_path):
     eng2.close()
 
 
+@pytest.mark.parametrize("shape", ["bench", "lens", "stride160", "bitmap"])
+def test_precompiled_kernel_is_the_one_an_engine_looks_up(monkeypatch, tmp_path, shape):
+    """what precompile stores is what an engine of the same plan and batch shape later looks up: with cache hits only
+    and an empty cache an engine runs the generic kernel; after precompile into that cache a new engine runs the
+    specialised one from its first submit, with the same counts.  Shapes: the bench shape, per-read lengths
+    (submit_device_q), stride 160 with lengths (the <8,4> generic instantiation: at stride 200 the 59-base scheme has
+    five words of offsets, which no specialised kernel takes) and the bit map on a small table."""
+    import torch
+    import ngs_barcode_count_amd as pkg
+    import workloads
+    monkeypatch.setenv("BC_JIT", "cached")
+    monkeypatch.setenv("BC_JIT_CACHE", str(tmp_path))
+    if shape == "bitmap":
+        monkeypatch.setenv("BC_BITMAP_MIN_ENTRIES", "1")
+    w = workloads.make("config3", n_sets=(4, 29, 31, 47))  # sizes neither build() nor another test compiles
+    n, R = 50_000, w.read_len
+    stride = 160 if shape == "stride160" else R
+    lens = shape in ("lens", "stride160")
+    dseq = torch.empty(n * stride, dtype=torch.uint8, device="cuda")
+    dqual = torch.empty(n * stride, dtype=torch.uint8, device="cuda")
+    w.synth.generate_device(0, None, 0, n, dseq.data_ptr(), dqual.data_ptr(), stride)
+    dlens = torch.full((n,), R, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+
+    def run():
+        eng = pkg.Engine(w.plan, device=0)
+        if lens:
+            eng.submit_device_q(dseq.data_ptr(), dqual.data_ptr(), n, stride, dlens.data_ptr(), dlens.data_ptr())
+        else:
+            eng.submit_device(dseq.data_ptr(), dqual.data_ptr(), n, stride, R)
+        got = eng.kernel_name(), eng.counters(), eng.result_rows()
+        eng.close()
+        return got
+
+    name, counters, rows = run()
+    assert name == ("match_count_kernel<8,4>" if stride == 160 else "match_count_kernel<4,2>"), name  # the cache missed
+    assert counters["total_reads"] == n
+    pkg.precompile(w.plan, stride=stride, read_len=R, lens=lens, cache_dir=str(tmp_path))
+    name2, counters2, rows2 = run()
+    assert name2.startswith("bc_jit_match_count"), name2
+    assert counters2 == counters
+    assert rows2 == rows
+
+
 @pytest.mark.parametrize("jit", ["0", "force"])
 def test_many_odd_sized_submits_equal_one_submit(monkeypatch, tmp_path, jit):
     """the pipelined persistent kernel at every kind of batch edge: 3 M reads cut into ~300 submits of random sizes
