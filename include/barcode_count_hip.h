@@ -170,6 +170,27 @@ int bc_engine_decode_index(const bc_engine *e, uint64_t dense_index, uint32_t *s
  * nothing is moved */
 int bc_engine_nonzero_entries(bc_engine *e, uint64_t *n);
 
+/* Single and double barcode enrichment (`--enrich`, ResultsEnrichment of info.rs:811-904) of a dense plan, computed on
+ * the device as index sums of the counts bc_engine_finish would hand out now: one pass over the table (and the bit map
+ * of two-level counting), random-barcode plans materialized first as bc_engine_finish does, the root's summed table
+ * after bc_engine_finish_all.  The table, the counters and the rows stay as they are; the call may come before or after
+ * bc_engine_finish, and more than once.
+ * Layout, with G = the number of counted barcodes, N_g = the size of known set g (engine index order),
+ * S = table_entries / (N_0 * .. * N_{G-1}) (the plan's sample count with a sample group, else 1), s = sample index and
+ * i_g = index into set g:
+ *   singles: single_counts[s * SUM + off_g + i_g], SUM = N_0 + .. + N_{G-1}, off_g = N_0 + .. + N_{g-1};
+ *   pairs in the order add_double produces them (info.rs:869-904): (0,1), (0,2), .., (0,G-1), (1,2), .., (G-2,G-1);
+ *   doubles: double_counts[s * P + poff_(g,h) + i_g * N_h + i_h], P = sum over pairs of N_g * N_h, poff_(g,h) = that
+ *   sum over the pairs before (g,h).
+ * All counts are u64 (marginals of u32 entries pass 2^32).  Doubles exist only for G >= 3 (the reference writes Double
+ * files only then, output.rs:176, 349): double_entries = 0 below.  A key of the reference's maps exists where its sum
+ * is not zero.  Device scratch: S * (SUM + P) * 8 bytes (BC_ERR_NOMEM when that cannot be allocated).
+ * Plans that keep raw captures (bc_plan_mode 2) have no index form: BC_ERR_UNSUPPORTED. */
+/* sizes of bc_engine_enrich's outputs, in u64 entries: S * SUM and S * P */
+int bc_engine_enrich_entries(const bc_engine *e, uint64_t *single_entries, uint64_t *double_entries);
+/* host pointers of those sizes; double_counts may be NULL (pairs are then skipped) */
+int bc_engine_enrich(bc_engine *e, uint64_t *single_counts, uint64_t *double_counts);
+
 /* Row i as the reference's Results holds it (info.rs:661-665): the sample key (a sample barcode
  * sequence, or "barcode" without a sample group) and the counted barcodes "b1,b2,.." as sequences.
  * Works for every plan, including those that keep raw captures (no sample / counted-barcode

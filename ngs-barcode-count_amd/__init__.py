@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import COUNTER_NAMES, SynthParams
 
 __all__ = ["Plan", "Engine", "Comm", "Synth", "SequenceFormat", "BarcodeConversions", "MaxSeqErrors", "SequenceErrors",
-           "Results", "SequenceParser", "fix_error", "BarcodeCountError", "COUNTER_NAMES"]
+           "Results", "ResultsEnrichment", "SequenceParser", "fix_error", "BarcodeCountError", "COUNTER_NAMES"]
 
 
 class BarcodeCountError(RuntimeError):
@@ -283,6 +283,34 @@ class Engine:
             raise err[0]
         _check(self._lib, rc)
         return n.value
+
+    def enrichment(self, doubles=True):
+        """bc_engine_enrich: single and pair counts of the counts finish() would hand out now, summed on the device ->
+        (singles, doubles): singles = [uint64 array (S, N_g) per counted barcode g]; doubles = {(g, h): uint64 array
+        (S, N_g, N_h)} for the pairs g < h, empty with fewer than 3 counted barcodes (or doubles=False).  S = samples
+        (1 without a sample group).  The engine's table, counters and rows stay as they are."""
+        ns, nd = C.c_uint64(), C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_enrich_entries(self._e, C.byref(ns), C.byref(nd)))
+        sizes = [self._lib.bc_plan_n_counted(self.plan._p, g) for g in range(self.plan.barcode_num)]
+        single = np.zeros(ns.value, dtype=np.uint64)
+        double = np.zeros(nd.value if doubles else 0, dtype=np.uint64)
+        _check(self._lib, self._lib.bc_engine_enrich(self._e, single.ctypes.data if single.size else None,
+                                                     double.ctypes.data if double.size else None))
+        S = ns.value // sum(sizes) if sum(sizes) else 0
+        single = single.reshape(S, sum(sizes))
+        singles, off = [], 0
+        for n in sizes:
+            singles.append(single[:, off:off + n])
+            off += n
+        pairs = {}
+        if double.size:
+            double = double.reshape(S, double.size // S)
+            off = 0
+            for g in range(len(sizes)):
+                for h in range(g + 1, len(sizes)):
+                    pairs[(g, h)] = double[:, off:off + sizes[g] * sizes[h]].reshape(S, sizes[g], sizes[h])
+                    off += sizes[g] * sizes[h]
+        return singles, pairs
 
     def reduce_all(self, comm, root=0):
         """bc_engine_reduce_all: the job's one exchange (collective over comm); -> the job's counters on the root,
@@ -569,6 +597,75 @@ class Results:
     def fill(self, rows):
         for sample, tup, count in rows:
             self.results_hashmap.setdefault(sample, {})[tup] = count
+
+
+class ResultsEnrichment:
+    """info.rs:811-904: single_hashmap / double_hashmap[sample key]["id1,,"] = count.  add_single / add_double build them
+    from rows as the reference does; fill() builds them from the engine's device-side marginals (Engine.enrichment)."""
+
+    def __init__(self):
+        self.single_hashmap = {}
+        self.double_hashmap = {}
+
+    def add_sample_barcodes(self, samples_barcodes):
+        for s in samples_barcodes:
+            self.single_hashmap[s] = {}
+            self.double_hashmap[s] = {}
+
+    def add_single(self, sample_id, barcode_string, count):  # info.rs:840-866
+        parts = barcode_string.split(",")
+        m = self.single_hashmap.get(sample_id, {})  # (an unknown sample: the add lands in a temporary)
+        for i in range(len(parts)):
+            key = ",".join(parts[x] if x == i else "" for x in range(len(parts)))
+            m[key] = m.get(key, 0) + count
+
+    def add_double(self, sample_id, barcode_string, count):  # info.rs:869-904
+        parts = barcode_string.split(",")
+        n = len(parts)
+        m = self.double_hashmap.get(sample_id, {})
+        for a in range(n - 1):
+            for b in range(a + 1, n):
+                key = ",".join(parts[x] if x in (a, b) else "" for x in range(n))
+                m[key] = m.get(key, 0) + count
+
+    def add_marginals(self, sample_keys, ids, singles, doubles):
+        """the maps from index marginals: sample_keys[s] = the key of sample s, ids[g][i] = the ID of sequence i of
+        counted set g, singles / doubles as Engine.enrichment returns them.  Sequences that share an ID add up, and a key
+        exists only where its sum is not zero (the reference makes one only when a row adds to it)."""
+        G = len(ids)
+        for s, key in enumerate(sample_keys):
+            m = self.single_hashmap.get(key)
+            if m is not None:
+                for g in range(G):
+                    row = singles[g][s]
+                    for i in np.flatnonzero(row):
+                        k = "," * g + ids[g][i] + "," * (G - 1 - g)
+                        m[k] = m.get(k, 0) + int(row[i])
+            m = self.double_hashmap.get(key)
+            if m is not None:
+                for (g, h), a in doubles.items():
+                    a = a[s]
+                    for i, j in zip(*np.nonzero(a)):
+                        k = "," * g + ids[g][i] + "," * (h - g) + ids[h][j] + "," * (G - 1 - h)
+                        m[k] = m.get(k, 0) + int(a[i, j])
+
+    def fill(self, engine):
+        """the maps of a dense plan's run from bc_engine_enrich, with the sample keys the reference's writers give them
+        (add_sample_barcodes over the Results keys, output.rs:74-97): every sample of the sample file, else "barcode"
+        when the scheme has no sample barcode -- and "barcode" also once a count lands there (a random-barcode run with a
+        sample file but no sample barcode, info.rs:792-801).  Every such key gets its maps, empty or not."""
+        plan = engine.plan
+        samples = [x for x, _ in plan.samples()]
+        results_keys = samples if samples else ([] if plan.sample_barcode else ["barcode"])
+        table_keys = samples if plan.sample_barcode else ["barcode"]  # the key of each sample index of the table
+        singles, doubles = engine.enrichment()
+        for s, k in enumerate(table_keys):
+            if k not in results_keys and singles and singles[0][s].any():
+                results_keys = results_keys + [k]
+        self.add_sample_barcodes([k for k in results_keys if k not in self.single_hashmap])
+        ids = [[i for _, i in plan.counted(g)] for g in range(plan.barcode_num)]
+        self.add_marginals(table_keys, ids, singles, doubles)
+        return self
 
 
 class SequenceParser:

@@ -81,6 +81,8 @@ ENGINE_API = {
     "bc_engine_finish_stream": (_int, [_vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "bc_engine_nonzero_entries": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_engine_decode_index": (_int, [_vp, _u64, C.POINTER(_u32), C.POINTER(_u32)]),
+    "bc_engine_enrich_entries": (_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "bc_engine_enrich": (_int, [_vp, _vp, _vp]),
     "bc_engine_timing": (_int, [_vp, _int]),
     "bc_engine_kernel_ms": (_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "bc_engine_kernel_ms_each": (_int, [_vp, C.POINTER(C.c_double), _u64, C.POINTER(C.c_uint64)]),

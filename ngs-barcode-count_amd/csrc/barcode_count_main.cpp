@@ -273,6 +273,7 @@ struct Run {
   std::vector<std::unordered_map<std::string, std::string>> counted_map;                  // sequence -> ID
   // WriteFiles state (output.rs:33-46)
   std::unordered_map<std::string, std::map<std::string, uint64_t>> single_hash, double_hash;
+  bool enrich_filled = false;  // single_hash / double_hash came from the device (fill_enrichment): no per-row adds
   std::unordered_set<std::string> compounds_written;
   std::vector<std::string> output_files;
   std::vector<uint64_t> output_counts;
@@ -399,6 +400,63 @@ void add_double(Run& r, const std::string& sample, const std::string& barcode_st
   }
 }
 
+// Dense plans: the whole of single_hash / double_hash at once from the device's marginal sums of the table
+// (bc_engine_enrich), in place of add_single / add_double on every row.  Keys are built as add_single / add_double
+// build them from a row's IDs; sequences of one group that share an ID add up; a key exists where its sum is not zero
+// (the string path makes one when a row, count >= 1, adds to it).  Maps of samples the writers do not know stay out,
+// as the string path's adds land in a temporary for them (info.rs:862).
+void add_sorted(std::map<std::string, uint64_t>& m, std::vector<std::pair<std::string, uint64_t>>& kv) {
+  std::sort(kv.begin(), kv.end());
+  for (size_t i = 0; i < kv.size();) {
+    uint64_t sum = 0;
+    size_t j = i;
+    for (; j < kv.size() && kv[j].first == kv[i].first; ++j) sum += kv[j].second;
+    m.emplace_hint(m.end(), std::move(kv[i].first), sum);  // (ascending keys into an empty map: constant time each)
+    i = j;
+  }
+  kv.clear();
+}
+
+// false: the engine has no device enrichment for the plan (the string path stays)
+bool fill_enrichment(Run& r, bool sample_group) {
+  const uint32_t G = r.barcode_num;
+  uint64_t n_single = 0, n_double = 0;
+  if (bc_engine_enrich_entries(r.engine, &n_single, &n_double) != BC_OK) return false;
+  std::vector<uint64_t> single(n_single), dbl(n_double);
+  const int rc = bc_engine_enrich(r.engine, single.data(), n_double ? dbl.data() : nullptr);
+  if (rc == BC_ERR_NOMEM) return false;  // (no room for the device scratch: the rows build the maps as before)
+  if (rc != BC_OK) die("%s", bc_last_error());
+  std::vector<uint64_t> off(G + 1, 0);
+  for (uint32_t g = 0; g < G; ++g) off[g + 1] = off[g] + r.counted[g].size();
+  const uint64_t sum_n = off[G], S = sum_n ? n_single / sum_n : 0, P = S ? n_double / S : 0;
+  auto commas_n = [](size_t n) { return std::string(n, ','); };
+  std::vector<std::pair<std::string, uint64_t>> kv;
+  for (uint64_t s = 0; s < S; ++s) {
+    const std::string key = sample_group ? r.samples[s].first : std::string("barcode");
+    if (std::find(r.sample_keys.begin(), r.sample_keys.end(), key) == r.sample_keys.end()) continue;
+    const uint64_t* srow = single.data() + s * sum_n;
+    for (uint32_t g = 0; g < G; ++g)
+      for (size_t i = 0; i < r.counted[g].size(); ++i)
+        if (const uint64_t v = srow[off[g] + i]) kv.emplace_back(commas_n(g) + r.counted[g][i].second + commas_n(G - 1 - g), v);
+    if (!kv.empty()) add_sorted(r.single_hash[key], kv);
+    if (!P) continue;
+    const uint64_t* drow = dbl.data() + s * P;
+    for (uint32_t g = 0; g + 1 < G; ++g)  // pairs in add_double's order: (0,1), (0,2), .., (1,2), ..
+      for (uint32_t h = g + 1; h < G; ++h) {
+        const size_t nh = r.counted[h].size();
+        for (size_t i = 0; i < r.counted[g].size(); ++i)
+          for (size_t j = 0; j < nh; ++j)
+            if (const uint64_t v = drow[i * nh + j])
+              kv.emplace_back(commas_n(g) + r.counted[g][i].second + commas_n(h - g) + r.counted[h][j].second +
+                                  commas_n(G - 1 - h), v);
+        drow += r.counted[g].size() * nh;
+      }
+    if (!kv.empty()) add_sorted(r.double_hash[key], kv);
+  }
+  r.enrich_filled = true;
+  return true;
+}
+
 enum Enriched { kSingle, kDouble, kFull };
 
 // add_counts_string (output.rs:199-361)
@@ -441,7 +499,7 @@ uint64_t add_counts_string(Run& r, const std::string& sample, const std::vector<
       }
     }
     r.sample_text += written + "," + std::to_string(count) + "\n";
-    if (type == kFull && r.args.enrich) {
+    if (type == kFull && r.args.enrich && !r.enrich_filled) {
       add_single(r, sample, written, count);
       if (r.barcode_num > 2) add_double(r, sample, written, count);
     }
@@ -808,6 +866,16 @@ int main(int argc, char** argv) {
       add_row(sample, tuple, r.counted.empty() ? std::string(tuple) : convert_code(r, tuple), cnt);
     }
   }
+  if (r.args.enrich && bc_plan_mode(r.plan) == 1 && r.counted.size() == r.barcode_num) {
+    // (an ID with a comma in it would split into other columns on the string path: such plans keep that path)
+    bool plain_ids = true;
+    for (const auto& set : r.counted)
+      for (const auto& kv : set) plain_ids = plain_ids && kv.second.find(',') == std::string::npos;
+    if (plain_ids) fill_enrichment(r, sample_group);
+  }
+  if (r.args.enrich && getenv("BC_ENRICH_VERBOSE"))  // (which path built the Single / Double maps; tests assert it)
+    fprintf(stderr, "[barcode-count] enrichment: %s\n",
+            r.enrich_filled ? "device marginal sums (bc_engine_enrich)" : "per-row string adds");
   write_counts_files(r);
   write_stats_file(r, start, start_ms, counters, total_reads);
   printf("\nTotal time: %s\n", elapsed_text(now_ms() - start_ms).c_str());  // main.rs:156-164

@@ -20,6 +20,7 @@
 
 #include "../../include/barcode_count_hip.h"
 #include "bc_kernel.h"
+#include "bc_enrich.h"
 #include "bc_fold.h"
 #include "bc_jit.h"
 #include "bc_plan.hpp"
@@ -1600,22 +1601,29 @@ int bc_engine_nonzero_entries(bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
+// What every reader of a dense plan's counts does first (bc_engine_finish, bc_engine_enrich): wait for the submits, and
+// for a random-barcode plan turn the key set into per-tuple counts unless that has been done for the current keys.
+// Afterwards entry i counts table[i] + bit i of the bit map (when e->bits_dirty: two-level counting, not folded).
+static int dense_counts_ready(bc_engine* e) {
+  int rc = bc_engine_sync(e);
+  if (rc) return rc;
+  if (e->h.plan.has_random && !e->table_materialized) return bc_engine_materialize_table(e);
+  return BC_OK;
+}
+
 // rows of either kind of plan, chunk by chunk (bc_engine_finish_stream); for sparse plans the chunks are cut from the
 // exported map
 static int finish_any(bc_engine* e, const std::function<int(uint64_t)>& on_total,
                       const std::function<int(const uint64_t*, const uint32_t*, uint64_t)>& on_rows, uint64_t* n_rows) {
-  int rc = bc_engine_sync(e);
-  if (rc) return rc;
+  int rc;
   if (e->h.plan.sparse) {
+    if ((rc = bc_engine_sync(e)) != BC_OK) return rc;
     uint64_t n = 0;
     if ((rc = finish_sparse(e, &n)) != BC_OK) return rc;
     if (n_rows) *n_rows = n;
     return BC_OK;  // (finish_sparse leaves the rows in e->row_idx / row_cnt; the callers below hand them on)
   }
-  if (e->h.plan.has_random && !e->table_materialized) {
-    rc = bc_engine_materialize_table(e);
-    if (rc) return rc;
-  }
+  if ((rc = dense_counts_ready(e)) != BC_OK) return rc;
   return finish_dense(e, on_total, on_rows, n_rows);
 }
 
@@ -1704,6 +1712,75 @@ int bc_engine_decode_index(const bc_engine* e, uint64_t dense_index, uint32_t* s
     di /= nr;
   }
   if (sample_idx) *sample_idx = (uint32_t)di;
+  return BC_OK;
+}
+
+// The shape of a dense plan's enrichment (bc_engine_enrich); false + set_error() for plans that have none.
+static bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples) {
+  const DevPlan& P = e->h.plan;
+  if (P.sparse) {
+    set_error(std::string(who) + ": the plan keeps raw captures, whose keys are sequences, not indices: enrich its rows "
+              "(bc_engine_row_text) on the host");
+    return false;
+  }
+  if (e->barcode_num > (uint32_t)kEnrichMaxG) {  // (cannot happen: a plan has at most kMaxGroups groups)
+    set_error(std::string(who) + ": more counted barcodes than the enrichment kernel takes");
+    return false;
+  }
+  memset(sh, 0, sizeof(*sh));
+  sh->G = e->barcode_num;
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  sh->inner = 1;
+  for (uint32_t g = 0; g < sh->G; ++g) {
+    sh->n[g] = P.groups[g0 + g].n_refs;
+    sh->single_off[g] = sh->sum_n;
+    sh->sum_n += sh->n[g];
+    sh->inner *= sh->n[g];
+  }
+  if (sh->G >= 3)  // (the reference writes Double files only then, output.rs:176, 349)
+    for (uint32_t g = 0; g + 1 < sh->G; ++g)
+      for (uint32_t h = g + 1; h < sh->G; ++h) {
+        sh->pair_off[enrich_pair_index((int)sh->G, (int)g, (int)h)] = sh->pairs;
+        sh->pairs += (uint64_t)sh->n[g] * sh->n[h];
+      }
+  *n_samples = sh->inner ? e->table_entries / sh->inner : 0;
+  return true;
+}
+
+int bc_engine_enrich_entries(const bc_engine* e, uint64_t* single_entries, uint64_t* double_entries) {
+  EnrichShape sh;
+  uint64_t S = 0;
+  if (!enrich_shape(e, "bc_engine_enrich_entries", &sh, &S)) return BC_ERR_UNSUPPORTED;
+  if (single_entries) *single_entries = S * sh.sum_n;
+  if (double_entries) *double_entries = S * sh.pairs;
+  return BC_OK;
+}
+
+// Single and pair counts as marginal sums of the dense table, in one pass over it on the device (bc_enrich.hip).  The
+// table, the bit map and the rows stay as they are.
+int bc_engine_enrich(bc_engine* e, uint64_t* single_counts, uint64_t* double_counts) {
+  EnrichShape sh;
+  uint64_t S = 0;
+  if (!enrich_shape(e, "bc_engine_enrich", &sh, &S)) return BC_ERR_UNSUPPORTED;
+  const uint64_t n_single = S * sh.sum_n, n_double = double_counts ? S * sh.pairs : 0;
+  if (n_single && !single_counts) {
+    set_error("bc_engine_enrich: single_counts is NULL");
+    return BC_ERR_INVALID;
+  }
+  int rc = dense_counts_ready(e);
+  if (rc) return rc;
+  if (n_single == 0) return BC_OK;
+  ScratchGuard g;
+  unsigned long long *d_single = nullptr, *d_double = nullptr;
+  HIP_TRY(g.dmalloc(&d_single, n_single * 8));
+  if (n_double) HIP_TRY(g.dmalloc(&d_double, n_double * 8));
+  HIP_TRY(hipMemsetAsync(d_single, 0, n_single * 8, e->stream));
+  if (n_double) HIP_TRY(hipMemsetAsync(d_double, 0, n_double * 8, e->stream));
+  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, d_single, d_double,
+                           e->stream));
+  HIP_TRY(hipMemcpyAsync(single_counts, d_single, n_single * 8, hipMemcpyDeviceToHost, e->stream));
+  if (n_double) HIP_TRY(hipMemcpyAsync(double_counts, d_double, n_double * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return BC_OK;
 }
 
