@@ -344,13 +344,65 @@ int bc_fastq_count(bc_engine *e, const char *fastq_path, uint64_t *total_reads, 
  * Shard boundaries are moved to the next record start ('@' line whose second-next line begins with '+'), so the shards
  * tile the file's records exactly and their totals add up to bc_fastq_count's -- for a file whose lines come in fours;
  * one that does not is refused (BC_ERR_INVALID: the reference frames from the file's first line, a shard cannot).  The
- * first-record check is the first shard's, the trailing partial record the last shard's.  A .gz stream cannot be entered
- * in the middle: shard 0 reads all of it, the others nothing. */
+ * first-record check is the first shard's, the trailing partial record the last shard's.  A BGZF file (see below) is
+ * sharded like a plain one, by its INFLATED bytes: every shard reads and inflates only the blocks that cover its
+ * records, and the end-of-stream quirks of a .gz input are the last shard's.  Any other .gz stream cannot be entered in
+ * the middle: shard 0 reads all of it, the others nothing. */
 int bc_fastq_count_shard(bc_engine *e, const char *fastq_path, uint32_t shard, uint32_t n_shards, uint64_t *total_reads,
                          bc_progress_fn progress, void *user);
 /* where a shard that nominally begins at byte `offset` of a plain FASTQ file really begins: the first record start at
  * or after it (the file's size when there is none).  Host logic only: no engine, no GPU. */
 int bc_fastq_record_start(const char *fastq_path, uint64_t offset, uint64_t *start);
+
+/* ---- BGZF: blocked gzip, inflated on the device ------------------------------------------------- */
+
+/* A *.fastq.gz file that is BGZF through and through (what bgzip and the htslib tools write: a chain of gzip members
+ * of at most 64 KiB of text each, every header giving its member's length) is not read through zlib: the compressed
+ * bytes go to the device, one wavefront inflates one block (all of RFC 1951, CRC32 and ISIZE checked there), and the
+ * framing kernels go on from the inflated text.  Every other .gz file keeps the single zlib stream.  Counts are the same
+ * either way.  Environment: BC_GZ_DEVICE=1 (default) | 0 (every .gz through zlib); BC_INGEST_VERBOSE=1: one line on
+ * stderr per bc_fastq_count* call (path taken, shard, blocks inflated, records counted). */
+
+/* Walks the member headers of a file (host only, no GPU).  BC_OK: the file is BGZF -- every member is deflate with
+ * FEXTRA and a 'BC' subfield of length 2, the chain offset += BSIZE + 1 tiles the file to its last byte, every ISIZE is
+ * at most 65536 (empty members, such as the 28-byte EOF marker, are ordinary blocks; the marker may be missing).
+ * BC_ERR_UNSUPPORTED: it is not, and bc_last_error says where the chain broke.  BC_ERR_INVALID: unreadable. */
+int bc_bgzf_scan(const char *path, uint64_t *n_blocks, uint64_t *inflated_bytes);
+/* bc_fastq_record_start for a BGZF file: `inflated_offset` and *start count inflated bytes.  Inflates only the blocks
+ * around the offset, with zlib on the host.  BC_ERR_UNSUPPORTED when the file is not BGZF. */
+int bc_fastq_gz_record_start(const char *path, uint64_t inflated_offset, uint64_t *start);
+
+/* one block of an inflate table */
+typedef struct bc_bgzf_block {
+  uint64_t src_off;  /* where the block's deflate stream (the member without header and trailer) starts in d_src */
+  uint64_t dst_off;  /* where its text goes in d_dst */
+  uint32_t src_len;  /* bytes of the deflate stream */
+  uint32_t isize;    /* ISIZE of the trailer: bytes of text */
+  uint32_t crc32;    /* CRC32 of the trailer */
+} bc_bgzf_block;
+
+/* per-block results of bc_bgzf_inflate_device */
+#define BC_INFLATE_OK 0
+#define BC_INFLATE_BAD_BLOCK_TYPE 1   /* BTYPE 3, or a stored block whose LEN / NLEN disagree */
+#define BC_INFLATE_BAD_CODE_LENGTHS 2
+#define BC_INFLATE_BAD_SYMBOL 3       /* invalid symbol, or a distance that reaches before the block's own text */
+#define BC_INFLATE_INPUT_OVERRUN 4
+#define BC_INFLATE_OUTPUT_OVERRUN 5
+#define BC_INFLATE_ISIZE_MISMATCH 6
+#define BC_INFLATE_CRC_MISMATCH 7
+
+/* Inflates n_blocks BGZF blocks that lie in device memory: d_src[0, src_bytes) holds the compressed bytes, `blocks`
+ * (host memory) says where each block's deflate stream is and where its text goes in d_dst[0, dst_bytes).  status
+ * (host memory, n_blocks words) receives BC_INFLATE_OK or what was wrong with the block; a bad block never reads
+ * outside its own stream nor writes outside its own [dst_off, dst_off + isize).  Runs on hip_stream (NULL: the default
+ * stream) and waits for it.  BC_OK even when blocks are bad (the status says so); BC_ERR_INVALID only for a table that
+ * contradicts src_bytes / dst_bytes (or a block above 65536 bytes either way). */
+int bc_bgzf_inflate_device(int device_id, void *hip_stream, const void *d_src, uint64_t src_bytes,
+                           const bc_bgzf_block *blocks, uint64_t n_blocks, void *d_dst, uint64_t dst_bytes,
+                           uint32_t *status);
+/* BGZF blocks inflated on the device for this engine since it was created (by bc_fastq_count*).  Read-only: does not
+ * wait for the device. */
+int bc_engine_gz_blocks_inflated(const bc_engine *e, uint64_t *n);
 
 /* ---- synthetic workloads (bench + full-size parity) -------------------------------------- */
 

@@ -238,6 +238,12 @@ class Engine:
         _check(self._lib, self._lib.bc_engine_count_log_folds(self._e, C.byref(n)))
         return n.value
 
+    def gz_blocks_inflated(self):
+        """BGZF blocks inflated on the device for this engine since it was created (0: every .gz went through zlib)"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_gz_blocks_inflated(self._e, C.byref(n)))
+        return n.value
+
     def sclk_mhz(self):
         """shader clock right now (0.3 ms probe kernel)"""
         v = C.c_double()

@@ -22,6 +22,14 @@ class SynthParams(C.Structure):
                 ("lowq_hi", C.c_uint8), ("n_molecules", C.c_uint64), ("zipf", C.c_uint32), ("reserved", C.c_uint32), ("geo_total", C.c_uint64)]
 
 
+class BgzfBlock(C.Structure):  # bc_bgzf_block
+    _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64), ("src_len", C.c_uint32), ("isize", C.c_uint32),
+                ("crc32", C.c_uint32)]
+
+
+INFLATE_STATUS = ["ok", "bad block type", "bad code lengths", "invalid symbol or distance", "input overrun",
+                  "output overrun", "ISIZE mismatch", "CRC32 mismatch"]
+
 _vp, _cp, _u32, _u64, _i32, _int, _sz = C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_int, C.c_size_t
 
 # name -> (restype, argtypes); one entry per function declared in the header
@@ -117,6 +125,10 @@ ENGINE_API = {
     "bc_fastq_count": (_int, [_vp, _cp, C.POINTER(C.c_uint64), _vp, _vp]),
     "bc_fastq_count_shard": (_int, [_vp, _cp, _u32, _u32, C.POINTER(C.c_uint64), _vp, _vp]),
     "bc_fastq_record_start": (_int, [_cp, _u64, C.POINTER(C.c_uint64)]),
+    "bc_bgzf_scan": (_int, [_cp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bc_fastq_gz_record_start": (_int, [_cp, _u64, C.POINTER(C.c_uint64)]),
+    "bc_bgzf_inflate_device": (_int, [_int, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "bc_engine_gz_blocks_inflated": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_comm_sum_u64": (_int, [_vp, C.POINTER(C.c_uint64), _int, _int]),
     "bc_synth_create": (_vp, [_vp, C.POINTER(SynthParams)]),
     "bc_synth_destroy": (None, [_vp]),

@@ -598,6 +598,7 @@ struct bc_engine {
   uint64_t log_cap = 0;              // entries allocated in d_log / d_grouped
   uint32_t* d_log = nullptr;
   uint32_t* d_grouped = nullptr;
+  uint64_t gz_blocks = 0;            // BGZF blocks inflated on the device for this engine (bc_engine_gz_blocks_inflated)
   uint64_t log_folds = 0;            // folds run since the engine was created (bc_engine_count_log_folds)
   uint32_t* d_fold_meta = nullptr;   // [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each
   unsigned long long* d_counters = nullptr;
@@ -2125,6 +2126,11 @@ int bc_engine_count_log_folds(const bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
+int bc_engine_gz_blocks_inflated(const bc_engine* e, uint64_t* n) {
+  *n = e->gz_blocks;
+  return BC_OK;
+}
+
 int bc_engine_sclk_mhz(bc_engine* e, double* mhz) {
   *mhz = 0.0;
   HIP_TRY(hipSetDevice(e->device));
@@ -2438,3 +2444,8 @@ int bc_synth_make_set(uint64_t seed, uint32_t n, uint32_t k, uint32_t min_dist, 
 }
 
 }  // extern "C"
+
+// the ingest path's count of BGZF blocks inflated for this engine (bc_bgzf.hpp)
+namespace bc {
+void engine_add_gz_blocks(bc_engine* e, uint64_t n) { e->gz_blocks += n; }
+}  // namespace bc

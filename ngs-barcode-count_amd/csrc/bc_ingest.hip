@@ -5,7 +5,8 @@
 // (RawSequenceRead::check_fastq_format, parse.rs:377-427).  The reference pushes one packed String per read onto a
 // mutex-guarded VecDeque; here the host only MOVES bytes and the device does the framing:
 //
-//   host     a reader team pread()s the file (page cache -> pinned chunk buffers, several threads; zlib for .gz),
+//   host     a reader team pread()s the file (page cache -> pinned chunk buffers, several threads; zlib for .gz,
+//            unless the file is BGZF: then the compressed bytes travel and the device inflates them, bc_inflate.hip),
 //   PCIe     the raw text goes to the device as it is (hipMemcpyAsync on the ingest stream),
 //   device   newline scan (count, prefix sum, positions), record table (where each record's sequence and quality
 //            line start, how long they are), then a gather into the fixed-stride sequence / quality batch the match
@@ -27,12 +28,14 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/barcode_count_hip.h"
+#include "bc_bgzf.hpp"
 #include "bc_plan.hpp"
 
 using namespace bc;
@@ -294,6 +297,15 @@ struct Slot {
   hipEvent_t framed = nullptr;     // the stats have arrived on the host
   hipEvent_t gathered = nullptr;   // the batch arrays are complete (ingest stream)
   hipEvent_t consumed = nullptr;   // the match kernel has read the batch arrays (engine stream)
+  // BGZF chunks: `pin` holds the compressed bytes of blocks [first_blk, first_blk + nblk) of the file's index, the
+  // inflate kernel writes their text behind the overlap of d_text
+  uint8_t* d_comp = nullptr;
+  bc_bgzf_block* blk_tab = nullptr;    // pinned host
+  bc_bgzf_block* d_blk_tab = nullptr;
+  uint32_t* blk_status = nullptr;      // pinned host
+  uint32_t* d_blk_status = nullptr;
+  size_t clen = 0, nblk = 0, first_blk = 0;
+  long long patch_at = -1;         // text offset of the stream's unterminated last character (it becomes '\n'), or -1
   size_t len = 0;                  // text bytes of the chunk held now
   size_t ov = 0;                   // bytes of overlap in front of them on the device
   unsigned long long file_off = 0; // file offset of the chunk's first byte
@@ -309,7 +321,27 @@ struct Ingest {
   Slot slot[kSlots];
   DevState* d_state = nullptr;
   bool gz = false;
+  bool bgzf = false;               // this call inflates on the device
+  size_t blk_cap = 0;              // blocks per chunk the BGZF buffers hold (0: not allocated yet)
+  const std::vector<BgzfMember>* members = nullptr;
+  std::string path;
+  uint64_t blocks_inflated = 0;    // this call
   uint32_t stride = 0, ragged_stride = 0;
+
+  // the buffers only BGZF input needs, made at the first such call
+  int alloc_bgzf() {
+    if (blk_cap) return BC_OK;
+    const size_t cap = chunk / 256 + 64;
+    for (Slot& s : slot) {
+      HIP_TRY(hipMalloc((void**)&s.d_comp, chunk + 16));
+      HIP_TRY(hipHostMalloc((void**)&s.blk_tab, cap * sizeof(bc_bgzf_block), hipHostMallocDefault));
+      HIP_TRY(hipMalloc((void**)&s.d_blk_tab, cap * sizeof(bc_bgzf_block)));
+      HIP_TRY(hipHostMalloc((void**)&s.blk_status, cap * sizeof(uint32_t), hipHostMallocDefault));
+      HIP_TRY(hipMalloc((void**)&s.d_blk_status, cap * sizeof(uint32_t)));
+    }
+    blk_cap = cap;
+    return BC_OK;
+  }
 
   int alloc() {
     n_blk_cap = (uint32_t)((kOverlap + chunk + kScanBlock - 1) / kScanBlock);
@@ -344,8 +376,10 @@ struct Ingest {
     for (Slot& s : slot) {
       if (s.pin) (void)hipHostFree(s.pin);
       if (s.stats) (void)hipHostFree(s.stats);
+      if (s.blk_tab) (void)hipHostFree(s.blk_tab);
+      if (s.blk_status) (void)hipHostFree(s.blk_status);
       void* dev[] = {s.d_stats, s.d_text, s.d_blk_cnt, s.d_blk_off, s.d_nl_pos, s.d_seq_at, s.d_qual_at, s.d_lens, s.d_qlens,
-                     s.d_out_seq, s.d_out_qual};
+                     s.d_out_seq, s.d_out_qual, s.d_comp, s.d_blk_tab, s.d_blk_status};
       for (void* p : dev)
         if (p) (void)hipFree(p);
       for (hipEvent_t ev : {s.uploaded, s.framed, s.gathered, s.consumed})
@@ -359,8 +393,13 @@ struct Ingest {
   int frame(int b, const Slot* prev) {
     Slot& s = slot[b];
     HIP_TRY(hipStreamWaitEvent(st, s.consumed, 0));  // the batch arrays of this slot may still be read by a match kernel
-    HIP_TRY(hipMemcpyAsync(s.d_text + kOverlap, s.pin, s.len, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(s.uploaded, st));
+    if (!bgzf) {
+      HIP_TRY(hipMemcpyAsync(s.d_text + kOverlap, s.pin, s.len, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipEventRecord(s.uploaded, st));
+    } else {
+      const int rc = inflate(s);
+      if (rc != BC_OK) return rc;
+    }
     s.ov = 0;
     if (prev) {
       s.ov = std::min(kOverlap, prev->ov + prev->len);
@@ -391,6 +430,37 @@ struct Ingest {
     s_text_len[b] = len;
     return BC_OK;
   }
+  // BGZF: compressed bytes and block table -> device, one wavefront inflates one block into the slot's text buffer, the
+  // statuses travel back with the chunk's stats
+  int inflate(Slot& s) {
+    HIP_TRY(hipMemcpyAsync(s.d_comp, s.pin, s.clen, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.d_blk_tab, s.blk_tab, s.nblk * sizeof(bc_bgzf_block), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s.uploaded, st));
+    HIP_TRY((hipError_t)bgzf_inflate_launch(st, s.d_comp, s.d_blk_tab, s.nblk, s.d_text + kOverlap, s.d_blk_status));
+    if (s.patch_at >= 0) HIP_TRY((hipError_t)bgzf_patch_newline_launch(st, s.d_text + kOverlap, (uint64_t)s.patch_at));
+    HIP_TRY(hipMemcpyAsync(s.blk_status, s.d_blk_status, s.nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return BC_OK;
+  }
+  // blocks that hold no text (EOF markers) in a chunk of their own: inflated and checked, nothing to frame
+  int inflate_only(int b) {
+    Slot& s = slot[b];
+    const int rc = inflate(s);
+    if (rc != BC_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return check_blocks(s);
+  }
+  // the statuses of a chunk's blocks (they have arrived): a damaged block ends the call
+  int check_blocks(const Slot& s) {
+    for (size_t k = 0; k < s.nblk; ++k) {
+      if (s.blk_status[k] == 0) continue;
+      set_error("read error in " + path + ": BGZF block at file offset " +
+                std::to_string((unsigned long long)(*members)[s.first_blk + k].file_off) + ": " + bgzf_status_name(s.blk_status[k]));
+      return BC_ERR_INVALID;
+    }
+    blocks_inflated += s.nblk;
+    engine_add_gz_blocks(engine, s.nblk);
+    return BC_OK;
+  }
   const uint8_t* s_text[kSlots] = {nullptr, nullptr, nullptr};
   unsigned long long s_text_len[kSlots] = {0, 0, 0};  // bytes of the framed text behind s_text
 
@@ -400,6 +470,10 @@ struct Ingest {
     HIP_TRY(hipEventSynchronize(s.framed));
     const ChunkStats cs = *s.stats;
     *n_rec_out = 0;
+    if (bgzf) {
+      const int rc = check_blocks(s);
+      if (rc != BC_OK) return rc;
+    }
     if (cs.start < 0) {
       set_error("a FASTQ record is longer than 4 MiB");
       return BC_ERR_INVALID;
@@ -474,6 +548,13 @@ struct Source {
     // (size = where this reader's share of the file ends: the file's end, or the shard's)
     if (pos >= size) return 0;
     cap = (size_t)std::min<unsigned long long>(cap, size - pos);
+    const long total = read_span(dst, pos, cap);
+    if (total > 0) pos += (unsigned long long)total;
+    return total;
+  }
+  // bytes [pos, pos + cap) of the file, as many as there are; -1 on error
+  long read_span(uint8_t* dst, unsigned long long pos, size_t cap) {
+    if (cap == 0) return 0;
     // page cache -> pinned memory, one slice per thread
     const size_t slice = (((cap + threads - 1) / threads) + 4095) & ~(size_t)4095;  // (never 0: cap may be a few bytes)
     std::vector<long> got(threads, 0);
@@ -501,7 +582,6 @@ struct Source {
       total += (size_t)got[t];
       if ((size_t)got[t] < std::min(cap, (size_t)(t + 1) * slice) - std::min(cap, (size_t)t * slice)) break;  // end of file inside this slice
     }
-    pos += total;
     return (long)total;
   }
 };
@@ -510,25 +590,23 @@ struct Source {
 // begins with '@' while the line two further down begins with '+' (a quality line may begin with '@', but then the line
 // two further down is a sequence line, which never begins with '+').  `size` when there is none; -1 on a read error or
 // when no record boundary is found within 16 MiB (no FASTQ record is that long: the framing kernels allow 4 MiB).
-long long record_start_at_or_after(int fd, unsigned long long off, unsigned long long size) {
+// `read_at(dst, n, at)` delivers bytes [at, at + n) of the text (fewer at its end; < 0: error): a plain file's bytes, or a
+// BGZF file's inflated ones, fetched `step` bytes at a time.
+using ReadAt = std::function<long(char* dst, size_t n, unsigned long long at)>;
+long long record_start_at_or_after(const ReadAt& read_at, unsigned long long off, unsigned long long size, size_t step = 1u << 20) {
   if (off == 0) return 0;
   if (off >= size) return (long long)size;
   const unsigned long long from = off - 1;  // (the byte before tells whether `off` itself starts a line)
   std::vector<char> buf;
-  const size_t step = 1u << 20, limit = 16u << 20;
+  const size_t limit = 16u << 20;
   for (;;) {
     const size_t have = buf.size();
     if (from + have >= size || have >= limit) break;
     const size_t want = (size_t)std::min<unsigned long long>(step, size - (from + have));
     buf.resize(have + want);
-    size_t got = 0;
-    while (got < want) {
-      const ssize_t n = pread(fd, buf.data() + have + got, want - got, (off_t)(from + have + got));
-      if (n < 0) return -1;
-      if (n == 0) break;
-      got += (size_t)n;
-    }
-    buf.resize(have + got);
+    const long got = read_at(buf.data() + have, want, from + have);
+    if (got < 0) return -1;
+    buf.resize(have + (size_t)got);
     const bool at_end = from + buf.size() >= size;
     // line starts inside the window (buffer offsets), from the first one at or after `off`
     size_t p = 0;
@@ -559,6 +637,24 @@ long long record_start_at_or_after(int fd, unsigned long long off, unsigned long
   return from + buf.size() >= size ? (long long)size : -1;
 }
 
+ReadAt plain_reader(int fd) {
+  return [fd](char* dst, size_t want, unsigned long long at) -> long {
+    size_t got = 0;
+    while (got < want) {
+      const ssize_t n = pread(fd, dst + got, want - got, (off_t)(at + got));
+      if (n < 0) return -1;
+      if (n == 0) break;
+      got += (size_t)n;
+    }
+    return (long)got;
+  };
+}
+// (a BGZF block holds at most 64 KiB of text: fetching by the block keeps the host inflate to the blocks around `off`)
+long long gz_record_start_at_or_after(BgzfHostReader& hr, unsigned long long off) {
+  return record_start_at_or_after([&hr](char* dst, size_t n, unsigned long long at) { return hr.read_at(dst, n, at); }, off,
+                                  hr.inflated, 64u << 10);
+}
+
 }  // namespace
 
 static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard, uint32_t n_shards, uint64_t* total_reads,
@@ -573,10 +669,37 @@ extern "C" int bc_fastq_record_start(const char* fastq_path, uint64_t offset, ui
     return BC_ERR_INVALID;
   }
   const off_t end = lseek(fd, 0, SEEK_END);
-  const long long at = record_start_at_or_after(fd, offset, end > 0 ? (unsigned long long)end : 0ull);
+  const long long at = record_start_at_or_after(plain_reader(fd), offset, end > 0 ? (unsigned long long)end : 0ull);
   close(fd);
   if (at < 0) {
     set_error("no FASTQ record boundary found (read error, or not 4-line FASTQ)");
+    return BC_ERR_INVALID;
+  }
+  *start = (uint64_t)at;
+  return BC_OK;
+}
+
+extern "C" int bc_fastq_gz_record_start(const char* path, uint64_t inflated_offset, uint64_t* start) {
+  *start = 0;
+  const std::string p = path ? path : "";
+  std::vector<BgzfMember> members;
+  BgzfHostReader hr;
+  std::string why;
+  const int rc = bgzf_index(p, &members, &hr.inflated, &why);
+  if (rc < 0) {
+    set_error("Failed to open file: " + p);
+    return BC_ERR_INVALID;
+  }
+  if (rc > 0) {
+    set_error("not BGZF: " + why);
+    return BC_ERR_UNSUPPORTED;
+  }
+  hr.fd = open(p.c_str(), O_RDONLY);
+  hr.members = &members;
+  const long long at = hr.fd < 0 ? -1 : gz_record_start_at_or_after(hr, inflated_offset);
+  if (hr.fd >= 0) close(hr.fd);
+  if (at < 0) {
+    set_error("no FASTQ record boundary found (read error, damaged block, or not 4-line FASTQ)");
     return BC_ERR_INVALID;
   }
   *start = (uint64_t)at;
@@ -606,35 +729,100 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     set_error("This program only works with *.fastq files and *.fastq.gz files.  The latter is still experimental");
     return BC_ERR_INVALID;
   }
-  Source src;
-  src.gz = gz;
+  // A .gz file that is BGZF through and through is inflated on the device, block by block (BC_GZ_DEVICE=0: never);
+  // every other one is a single zlib stream on the host.
+  std::vector<BgzfMember> members;
+  uint64_t inflated = 0;
+  bool bgzf = false;
   if (gz) {
+    const char* ev = getenv("BC_GZ_DEVICE");
+    std::string why;
+    if (!(ev && ev[0] == '0' && !ev[1])) bgzf = bgzf_index(path, &members, &inflated, &why) == 0;
+  }
+  const bool verbose = [] {
+    const char* ev = getenv("BC_INGEST_VERBOSE");
+    return ev && ev[0] && !(ev[0] == '0' && !ev[1]);
+  }();
+  uint64_t total = 0, blocks_this_call = 0;
+  auto say = [&](int code) {
+    if (verbose)
+      fprintf(stderr, "[bc ingest] %s: path %s, shard %u/%u, %llu BGZF blocks inflated on the device, %llu records counted%s\n",
+              path.c_str(), bgzf ? "bgzf-device" : gz ? "gzread" : "plain", shard, n_shards, (unsigned long long)blocks_this_call,
+              (unsigned long long)total, code == BC_OK ? "" : " (failed)");
+  };
+  Source src;
+  src.gz = gz && !bgzf;
+  if (bgzf) {
+    src.fd = open(path.c_str(), O_RDONLY);
+  } else if (gz) {
     src.zf = gzopen(path.c_str(), "rb");  // multi-member aware (flate2 MultiGzDecoder, input.rs:63)
     if (src.zf) gzbuffer(src.zf, 4 << 20);
   } else {
     src.fd = open(path.c_str(), O_RDONLY);
   }
-  if ((gz && !src.zf) || (!gz && src.fd < 0)) {
+  if ((src.gz && !src.zf) || (!src.gz && src.fd < 0)) {
     set_error("Failed to open file: " + path);
     return BC_ERR_INVALID;
   }
-  if (!gz) {
+  if (!gz) {  // (a BGZF file is read by its index: `size` stays 0)
     const off_t end = lseek(src.fd, 0, SEEK_END);
     src.size = end > 0 ? (unsigned long long)end : 0ull;
   }
   // One shard of several (one per GPU of a job): the records that START inside this shard's share of the bytes.  A gz
   // stream cannot be entered in the middle: its first shard takes all of it, the others have nothing to read.
   const bool last_shard = shard + 1 == n_shards;
-  if (n_shards > 1) {
+  // BGZF: the shard's share of the INFLATED bytes [text_a, text_b), both ends on record starts, and the blocks that
+  // cover it; the text of a shared first block before text_a is skipped by the framing (the device state starts there)
+  unsigned long long text_a = 0, text_b = inflated;
+  size_t first_member = 0, end_member = members.size();
+  std::vector<uint8_t> last_text;  // the file's last block that holds text, inflated on the host (last shard)
+  size_t last_text_member = (size_t)-1;
+  if (bgzf) {
+    BgzfHostReader hr;
+    hr.fd = src.fd;
+    hr.members = &members;
+    hr.inflated = inflated;
+    if (n_shards > 1) {
+      const long long a = gz_record_start_at_or_after(hr, inflated / n_shards * shard);
+      const long long b = last_shard ? (long long)inflated : gz_record_start_at_or_after(hr, inflated / n_shards * (shard + 1));
+      if (a < 0 || b < 0) {
+        close(src.fd);
+        set_error("no FASTQ record boundary found near a shard boundary of " + path + " (read error, or not 4-line FASTQ)");
+        say(BC_ERR_INVALID);
+        return BC_ERR_INVALID;
+      }
+      text_a = (unsigned long long)a;
+      text_b = (unsigned long long)std::max(a, b);
+      auto starts_after = [](unsigned long long v, const BgzfMember& m) { return v < m.out_off; };
+      if (shard != 0) first_member = (size_t)(std::upper_bound(members.begin(), members.end(), text_a, starts_after) - members.begin()) - 1;
+      if (!last_shard) {
+        end_member = (size_t)(std::lower_bound(members.begin(), members.end(), text_b,
+                                               [](const BgzfMember& m, unsigned long long v) { return m.out_off < v; }) -
+                              members.begin());
+        if (text_b == text_a || end_member < first_member) end_member = first_member;  // no record starts in this shard
+      }
+    }
+    if (last_shard) {
+      for (size_t k = members.size(); k-- > first_member;)
+        if (members[k].isize) {
+          last_text_member = k;
+          break;
+        }
+      // (a damaged block is the device's to report: here it only means "nothing to patch")
+      if (last_text_member != (size_t)-1 && !bgzf_inflate_host(src.fd, members[last_text_member], &last_text)) last_text.clear();
+    }
+  }
+  if (n_shards > 1 && !bgzf) {
     if (gz) {
       if (shard != 0) {
         gzclose(src.zf);
+        say(BC_OK);
         return BC_OK;
       }
     } else {
       const unsigned long long size = src.size;
-      const long long a = record_start_at_or_after(src.fd, size / n_shards * shard, size);
-      const long long b = last_shard ? (long long)size : record_start_at_or_after(src.fd, size / n_shards * (shard + 1), size);
+      const long long a = record_start_at_or_after(plain_reader(src.fd), size / n_shards * shard, size);
+      const long long b = last_shard ? (long long)size : record_start_at_or_after(plain_reader(src.fd), size / n_shards * (shard + 1), size);
       if (a < 0 || b < 0) {
         close(src.fd);
         set_error("no FASTQ record boundary found near a shard boundary of " + path + " (read error, or not 4-line FASTQ)");
@@ -649,9 +837,15 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
 
   // chunk size: a multiple of 16 (the device reads the text 16 bytes at a time), no larger than the file needs;
   // BC_INGEST_CHUNK is for tests, which want records to straddle chunks in small files
-  size_t chunk = gz ? (32u << 20) : (size_t)std::min<unsigned long long>(128u << 20, ((src.size >> 20) + 1) << 20);
+  size_t chunk = bgzf  ? (size_t)std::min<unsigned long long>(128u << 20, (((text_b - text_a) >> 20) + 1) << 20)
+                 : gz  ? (32u << 20)
+                       : (size_t)std::min<unsigned long long>(128u << 20, ((src.size >> 20) + 1) << 20);
   if (const char* ev = getenv("BC_INGEST_CHUNK")) chunk = (size_t)std::max(4096L, atol(ev));
   chunk = (chunk + 15) & ~(size_t)15;
+  // BGZF chunks are cut at block boundaries: text of at most `fill_cap` bytes, but always a whole block, so the
+  // buffers hold at least the largest block there can be
+  const size_t fill_cap = chunk;
+  if (bgzf) chunk = std::max<size_t>(chunk, 65536 + 16);
   // The pinned and device buffers of the last call are kept for the next one on the same device with the same
   // chunk size (pinning a few hundred MiB costs more than reading a small file); one call at a time per process.
   static std::mutex g_mu;
@@ -678,37 +872,64 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
       rc = BC_ERR_HIP;
     }
     if (rc == BC_OK) rc = g_cached->alloc();
+    if (rc == BC_OK && bgzf) rc = g_cached->alloc_bgzf();
     if (rc != BC_OK) {
       g_cached->release();
       delete g_cached;
       g_cached = nullptr;
-      if (gz) gzclose(src.zf); else close(src.fd);
+      if (src.gz) gzclose(src.zf); else close(src.fd);
+      say(rc);
       return rc;
     }
+  }
+  if (bgzf && (rc = g_cached->alloc_bgzf()) != BC_OK) {  // (a cached set of buffers that has not seen BGZF yet)
+    g_cached->release();
+    delete g_cached;
+    g_cached = nullptr;
+    close(src.fd);
+    say(rc);
+    return rc;
   }
   Ingest& in = *g_cached;
   in.engine = e;
   in.gz = gz;
+  in.bgzf = bgzf;
+  in.members = &members;
+  in.path = path;
+  in.blocks_inflated = 0;
   in.engine_stream = (hipStream_t)bc_engine_hip_stream(e);
   in.stride = in.ragged_stride = 0;
   for (Slot& sl : in.slot) {
     sl.len = sl.ov = 0;
     sl.file_off = 0;
     sl.eof = false;
+    sl.clen = sl.nblk = sl.first_blk = 0;
+    sl.patch_at = -1;
   }
   auto finish = [&](int code) {
     (void)hipStreamSynchronize(in.st);
     (void)bc_engine_sync(e);  // the match kernels read the batch arrays, which the next call reuses
-    if (gz)
+    if (src.gz)
       gzclose(src.zf);
     else
       close(src.fd);
+    blocks_this_call = in.blocks_inflated;
+    say(code);
     return code;
   };
   if (hipMemsetAsync(in.d_state, 0, sizeof(DevState), in.st) != hipSuccess) {
     set_error("bc_fastq_count: hipMemsetAsync failed");
     return finish(BC_ERR_HIP);
   }
+  if (bgzf && text_a) {  // the shard's first record: the framing starts there
+    const DevState first{text_a};
+    if (hipMemcpyAsync(in.d_state, &first, sizeof first, hipMemcpyHostToDevice, in.st) != hipSuccess ||
+        hipStreamSynchronize(in.st) != hipSuccess) {
+      set_error("bc_fastq_count: setting the shard's start failed");
+      return finish(BC_ERR_HIP);
+    }
+  }
+  const bool patch_last = bgzf && last_shard && !last_text.empty() && last_text.back() != '\n';
 
   // the reader team runs ahead of the device by the slots that are free: a producer thread fills, this thread frames
   std::mutex mu;
@@ -726,6 +947,52 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
       }
       Slot& s = in.slot[i % kSlots];
       (void)hipEventSynchronize(s.uploaded);  // the slot's previous text has left for the device
+      if (bgzf) {
+        // the next run of blocks whose text fits the chunk (at least one block), their bytes read as one span
+        const size_t from = first_member + (size_t)off;  // (`off` counts blocks here)
+        size_t upto = from;
+        unsigned long long text = 0, comp = 0;
+        while (upto < end_member) {
+          const BgzfMember& m = members[upto];
+          if (upto > from && (text + m.isize > fill_cap || comp + m.total > in.chunk || upto - from >= in.blk_cap)) break;
+          text += m.isize;
+          comp += m.total;
+          ++upto;
+        }
+        const long n = upto > from ? src.read_span(s.pin, members[from].file_off, (size_t)comp) : 0;
+        const bool bad = n < 0 || (unsigned long long)n != comp;
+        const unsigned long long text_off = upto > from ? members[from].out_off : text_b;
+        long long patch_at = -1;
+        for (size_t k = from; k < upto; ++k) {
+          const BgzfMember& m = members[k];
+          bc_bgzf_block& t = s.blk_tab[k - from];
+          t.src_off = m.file_off - members[from].file_off + m.payload_off;
+          t.dst_off = m.out_off - text_off;
+          t.src_len = m.payload_len;
+          t.isize = m.isize;
+          t.crc32 = m.crc32;
+          if (patch_last && k == last_text_member) patch_at = (long long)(t.dst_off + m.isize - 1);
+        }
+        const bool last = bad || upto >= end_member;
+        // (a shard that does not end the file stops at its last record's end, inside its last block)
+        if (text_off + text > text_b) text = text_b > text_off ? text_b - text_off : 0;
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          if (bad) read_error = true;
+          s.len = bad ? 0 : (size_t)text;
+          s.clen = (size_t)comp;
+          s.nblk = bad ? 0 : upto - from;
+          s.first_blk = from;
+          s.patch_at = patch_at;
+          s.file_off = text_off;
+          s.eof = last;
+          filled_upto = i + 1;
+        }
+        cv.notify_all();
+        if (last) return;
+        off += upto - from;
+        continue;
+      }
       const long n = src.fill(s.pin, in.chunk);
       const bool last = n <= 0 || (size_t)n < in.chunk || src.at_end();
       {
@@ -742,7 +1009,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     }
   });
 
-  uint64_t total = 0, lines_after_last_record = 0;
+  uint64_t lines_after_last_record = 0;
   bool last_byte_newline = true, any_bytes = false, appended_newline = false, gz_last_char_dropped = false;
   bool test = shard == 0;  // (the file's first record is the first shard's)
   int pending = -1;  // chunk framed but not yet submitted
@@ -762,12 +1029,26 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     if (s.len) {
       any_bytes = true;
       if (test) {  // first record only (input.rs:139-142, parse.rs:377-394): lines 1 and 2 of the file
-        const char* t = (const char*)s.pin;
-        const char* e1 = (const char*)memchr(t, '\n', s.len);
-        const char* e2 = e1 ? (const char*)memchr(e1 + 1, '\n', s.len - (size_t)(e1 + 1 - t)) : nullptr;
+        // (BGZF: the pinned buffer holds compressed bytes; the chunk's first blocks are inflated on the host, as far as
+        // the check looks.  A damaged block is the device's to report.)
+        std::vector<uint8_t> head;
+        if (in.bgzf) {
+          std::vector<uint8_t> one;
+          size_t lines = 0;
+          for (size_t k = s.first_blk; k < s.first_blk + s.nblk && lines < 5; ++k) {
+            if (!bgzf_inflate_host(src.fd, members[k], &one)) break;
+            lines += (size_t)std::count(one.begin(), one.end(), (uint8_t)'\n');
+            head.insert(head.end(), one.begin(), one.end());
+          }
+          if (head.size() > s.len) head.resize(s.len);
+        }
+        const char* t = in.bgzf ? (const char*)head.data() : (const char*)s.pin;
+        const size_t tlen = in.bgzf ? head.size() : s.len;  // the text the check may look at
+        const char* e1 = tlen ? (const char*)memchr(t, '\n', tlen) : nullptr;
+        const char* e2 = e1 ? (const char*)memchr(e1 + 1, '\n', tlen - (size_t)(e1 + 1 - t)) : nullptr;
         // (a file of fewer than four whole lines never posts a record, so the reference never looks at it)
-        const char* e3 = e2 ? (const char*)memchr(e2 + 1, '\n', s.len - (size_t)(e2 + 1 - t)) : nullptr;
-        const bool whole = e3 && (memchr(e3 + 1, '\n', s.len - (size_t)(e3 + 1 - t)) || (eof && !gz && (size_t)(e3 + 1 - t) < s.len));
+        const char* e3 = e2 ? (const char*)memchr(e2 + 1, '\n', tlen - (size_t)(e2 + 1 - t)) : nullptr;
+        const bool whole = e3 && (memchr(e3 + 1, '\n', tlen - (size_t)(e3 + 1 - t)) || (eof && !gz && (size_t)(e3 + 1 - t) < tlen));
         if (whole) {
           size_t n1 = (size_t)(e1 - t), n2 = (size_t)(e2 - (e1 + 1));
           if (!gz && n1 && t[n1 - 1] == '\r') --n1;
@@ -783,7 +1064,14 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
         test = false;
         if (rc != BC_OK) break;
       }
-      if (eof && s.pin[s.len - 1] != '\n') {
+      if (in.bgzf) {
+        // the unterminated last character of a gz stream becomes the missing newline (see below): on the device, after
+        // the inflate kernel
+        if (s.patch_at >= 0) {
+          last_byte_newline = false;
+          gz_last_char_dropped = true;
+        }
+      } else if (eof && s.pin[s.len - 1] != '\n') {
         last_byte_newline = false;
         if (!gz) {  // lines() hands the last line over without its newline (input.rs:44): framing-wise it has one
           s.pin[s.len++] = '\n';
@@ -798,6 +1086,14 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
         }
       }
       rc = in.frame(i % kSlots, i > 0 ? &in.slot[(i - 1) % kSlots] : nullptr);
+      if (rc != BC_OK) break;
+    } else if (in.bgzf && s.nblk) {
+      if (!eof) {  // (thousands of empty blocks in a row, in the middle of the file)
+        set_error("a BGZF chunk of " + path + " holds no text: not supported by the engine");
+        rc = BC_ERR_UNSUPPORTED;
+        break;
+      }
+      rc = in.inflate_only(i % kSlots);
       if (rc != BC_OK) break;
     }
     // the chunk before this one: its stats are in (or about to be); count it while this one is being framed
@@ -849,14 +1145,16 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     // the device counted)
     (void)gz_last_char_dropped;
     (void)appended_newline;
-    if (!last_shard && !(gz && shard == 0) && seen != 0) {
+    if (!last_shard && !(gz && !bgzf && shard == 0) && seen != 0) {
       // a shard that does not end the file ends on a record boundary; lines left over mean the file's lines do not
       // come in fours from where this shard started -- the reference, framing from the file's first line, would read
       // it differently from here on
       set_error("the lines of " + path + " do not come in records of four: run it on one GPU");
       return finish(BC_ERR_INVALID);
     }
-    if (gz && seen == 3 && last_counted_slot >= 0) {
+    // (the end of the stream is the last shard's: a BGZF file's other shards end on a record boundary)
+    const bool gz_end = gz && (!bgzf || last_shard);
+    if (gz_end && seen == 3 && last_counted_slot >= 0) {
       // The gz loop hands read() one more, empty line at the end of the stream (input.rs:69-73).  After three lines of
       // a record that makes "line 4": the reference posts the partial record -- header, sequence, '+' line and an EMPTY
       // quality line (post() pops the last character, unpack() fills what lines there are: parse.rs:236-267) -- and its
@@ -900,7 +1198,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
       }
     }
     if (seen > 0 && seen < 4) total += 1;  // a trailing partial record is counted when its first line is seen (input.rs:128-130)
-    if (gz) {
+    if (gz_end) {
       // the gz loop calls read("") once more at EOF (input.rs:69-73): when that lands on "line 1" the total grows
       // by one (README.md:159 vs 176)
       if (seen % 4 == 0) total += 1;
