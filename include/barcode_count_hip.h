@@ -191,6 +191,30 @@ int bc_engine_enrich_entries(const bc_engine *e, uint64_t *single_entries, uint6
 /* host pointers of those sizes; double_counts may be NULL (pairs are then skipped) */
 int bc_engine_enrich(bc_engine *e, uint64_t *single_counts, uint64_t *double_counts);
 
+/* The counts files of a dense plan as CSV text, written on the device from the counts bc_engine_finish would hand out
+ * now: the same preamble as bc_engine_enrich (submits waited for, a random-barcode plan materialized, the bit map of
+ * two-level counting read as it stands, the root's summed table after bc_engine_finish_all).  The table, the counters and
+ * the rows stay as they are; the calls may come before or after bc_engine_finish, and more than once.
+ * Layout, with G = the number of counted barcodes, T = N_0 * .. * N_{G-1} tuples per sample, id_g = the ID
+ * (bc_plan_counted_id) of the tuple's index into set g, copied byte for byte:
+ *   bc_engine_render_counts: for sample index s (0 for a plan without a sample group) one line per tuple whose count is
+ *     not zero:  id_0,id_1,..,id_{G-1},count\n
+ *   bc_engine_render_merged: for the ordered list sample_idx[0 .. n_samples) (a sample may come twice; any order) one
+ *     line per tuple for which some LISTED sample counts:  id_0,..,id_{G-1},c_0,c_1,..\n  with c_k the count of sample
+ *     sample_idx[k], 0 written as "0".
+ * Order: ascending tuple index t = sum_g i_g * prod_{k>g} N_k (the dense index within the sample's slice; the last
+ * counted barcode varies fastest), so the text is the same on every run.  No header line.
+ * The text reaches `fn` in chunks of at most BC_RENDER_CHUNK_BYTES (default 64 MiB; never less than the longest
+ * possible line) through two staging buffers, the device writing one while fn reads the other; device memory is those
+ * two buffers + 12 bytes per 1024 tuples (BC_ERR_NOMEM when that cannot be allocated; the engine stays usable).
+ * Plans that keep raw captures (bc_plan_mode 2) have no index form: BC_ERR_UNSUPPORTED. */
+/* a chunk of text, valid during the call; always ends with '\n'; return 0 to go on, else the render stops (BC_ERR_STATE) */
+typedef int (*bc_text_fn)(const char *text, size_t n, void *user);
+/* n_rows (may be NULL): the number of lines */
+int bc_engine_render_counts(bc_engine *e, uint32_t sample_idx, bc_text_fn fn, void *user, uint64_t *n_rows);
+int bc_engine_render_merged(bc_engine *e, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn, void *user,
+                            uint64_t *n_rows);
+
 /* Row i as the reference's Results holds it (info.rs:661-665): the sample key (a sample barcode
  * sequence, or "barcode" without a sample group) and the counted barcodes "b1,b2,.." as sequences.
  * Works for every plan, including those that keep raw captures (no sample / counted-barcode

@@ -290,6 +290,42 @@ class Engine:
         _check(self._lib, rc)
         return n.value
 
+    def _render(self, call, on_text):
+        out, err = bytearray(), []
+
+        def cb(tp, n, _user):
+            try:
+                chunk = C.string_at(tp, n)
+                if on_text is None:
+                    out.extend(chunk)
+                else:
+                    on_text(chunk)
+                return 0
+            except Exception as ex:  # never let an exception cross the C frames
+                err.append(ex)
+                return 1
+
+        fn = _lib.TEXT_FN(cb)
+        n = C.c_uint64()
+        rc = call(fn, C.byref(n))
+        if err:
+            raise err[0]
+        _check(self._lib, rc)
+        return n.value if on_text is not None else bytes(out)
+
+    def render_counts(self, sample=0, on_text=None):
+        """bc_engine_render_counts: the lines of sample index `sample`'s counts file (no header), written on the device,
+        in ascending dense-index order: b"id_0,..,id_{G-1},count\\n" per tuple that counts.  -> bytes; with on_text= every
+        chunk (bytes, ends with a newline) goes to that callable as it leaves the device and the line count returns."""
+        return self._render(lambda fn, n: self._lib.bc_engine_render_counts(self._e, int(sample), fn, None, n), on_text)
+
+    def render_merged(self, samples, on_text=None):
+        """bc_engine_render_merged: the merged file's lines (no header) for the sample indices `samples` as columns, in
+        that order: one line per tuple that counts in any LISTED sample, zero counts written as 0."""
+        cols = np.ascontiguousarray(list(samples), dtype=np.uint32)
+        return self._render(lambda fn, n: self._lib.bc_engine_render_merged(
+            self._e, cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
+
     def enrichment(self, doubles=True):
         """bc_engine_enrich: single and pair counts of the counts finish() would hand out now, summed on the device ->
         (singles, doubles): singles = [uint64 array (S, N_g) per counted barcode g]; doubles = {(g, h): uint64 array

@@ -14,6 +14,7 @@ COUNTER_NAMES = ["matched", "constant_region", "sample_barcode", "barcode", "dup
 
 
 ROWS_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint64, C.c_void_p)  # bc_rows_fn
+TEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)  # bc_text_fn
 
 
 class SynthParams(C.Structure):
@@ -91,6 +92,8 @@ ENGINE_API = {
     "bc_engine_decode_index": (_int, [_vp, _u64, C.POINTER(_u32), C.POINTER(_u32)]),
     "bc_engine_enrich_entries": (_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "bc_engine_enrich": (_int, [_vp, _vp, _vp]),
+    "bc_engine_render_counts": (_int, [_vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_render_merged": (_int, [_vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "bc_engine_timing": (_int, [_vp, _int]),
     "bc_engine_kernel_ms": (_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "bc_engine_kernel_ms_each": (_int, [_vp, C.POINTER(C.c_double), _u64, C.POINTER(C.c_uint64)]),

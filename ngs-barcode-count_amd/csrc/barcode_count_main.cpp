@@ -279,6 +279,9 @@ struct Run {
   std::vector<uint64_t> output_counts;
   uint64_t merged_count = 0;
   std::string merge_text, sample_text;
+  // the full-counts files as text from the device (bc_engine_render_counts / _merged): no rows on the host at all
+  bool device_writers = false;
+  std::unordered_map<std::string, uint32_t> sample_index;  // sample key -> the engine's sample index
 };
 
 std::string format_display(const Run& r) {  // info.rs:313-335
@@ -462,8 +465,8 @@ enum Enriched { kSingle, kDouble, kFull };
 // add_counts_string (output.rs:199-361)
 uint64_t add_counts_string(Run& r, const std::string& sample, const std::vector<std::string>& samples, Enriched type) {
   std::vector<Run::Row> enriched_rows;
-  const std::unordered_map<std::string, std::map<std::string, uint64_t>> holder =
-      type == kSingle ? r.single_hash : (type == kDouble ? r.double_hash : decltype(r.single_hash)());
+  static const decltype(r.single_hash) none;
+  const auto& holder = type == kSingle ? r.single_hash : (type == kDouble ? r.double_hash : none);
   if (type != kFull)
     for (const auto& kv : holder.at(sample)) enriched_rows.push_back({kv.first, kv.first, kv.second});
   const std::vector<Run::Row>& rows = type == kFull ? r.results[sample] : enriched_rows;
@@ -564,6 +567,34 @@ void write_enriched_files(Run& r, Enriched type) {  // output.rs:364-485
   }
 }
 
+// The device path of a full-counts file: the header, then the text chunks as they leave the device.  stdout gets what
+// add_counts_string prints for that many rows (its lines depend on the row count alone).
+int text_to_file(const char* text, size_t n, void* user) { return fwrite(text, 1, n, (FILE*)user) == n ? 0 : 1; }
+uint64_t render_file(Run& r, const std::string& name, const std::string& head, const std::vector<uint32_t>& cols, bool merged) {
+  std::string path = r.args.output_dir;
+  if (!path.empty() && path.back() != '/') path.push_back('/');
+  path += name;
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) die("cannot create %s", path.c_str());
+  if (fwrite(head.data(), 1, head.size(), f) != head.size()) die("%s: write failed", path.c_str());
+  uint64_t n = 0;
+  const int rc = merged ? bc_engine_render_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
+                        : bc_engine_render_counts(r.engine, cols[0], text_to_file, f, &n);
+  if (rc != BC_OK) die("%s: %s", path.c_str(), ferror(f) ? "write failed" : bc_last_error());
+  if (fclose(f) != 0) die("%s: write failed", path.c_str());
+  return n;
+}
+// what add_counts_string prints while it walks n rows: a line every 50,000 rows, and the total
+void print_rows_progress(uint64_t n) {
+  for (uint64_t k = 50000; k <= n; k += 50000) printf("Barcodes counted: %s\r", commas(k).c_str());
+  printf("Barcodes counted: %s\r\n", commas(n).c_str());
+}
+uint64_t render_sample_file(Run& r, const std::string& sample, const std::string& name, const std::string& head) {
+  const uint64_t n = render_file(r, name, head, {r.sample_index.at(sample)}, false);
+  print_rows_progress(n);
+  return n;
+}
+
 void write_counts_files(Run& r) {  // output.rs:74-181
   auto samples = ordered_samples(r, r.sample_keys);
   if (r.args.enrich)
@@ -586,6 +617,10 @@ void write_counts_files(Run& r) {  // output.rs:74-181
     const std::string file_name = r.args.prefix + "_" + sample_name(r, sb) + "_counts.csv";
     printf("%s\n", file_name.c_str());
     r.output_files.push_back(file_name);
+    if (r.device_writers) {
+      r.output_counts.push_back(render_sample_file(r, sb, file_name, header));
+      continue;
+    }
     r.sample_text += header;
     const uint64_t count = add_counts_string(r, sb, samples, kFull);
     write_file(r, file_name, r.sample_text);
@@ -595,9 +630,14 @@ void write_counts_files(Run& r) {  // output.rs:74-181
   if (r.args.merge_output) {
     const std::string merged = r.args.prefix + "_counts.all.csv";
     printf("%s\n", merged.c_str());
+    if (r.device_writers) {  // the columns in the header's order; a row per tuple that counts in any of them
+      std::vector<uint32_t> cols;
+      for (const auto& sb : samples) cols.push_back(r.sample_index.at(sb));
+      r.merged_count = render_file(r, merged, r.merge_text, cols, true);
+    }
     printf("Barcodes counted: %s\n", commas(r.merged_count).c_str());
     r.output_files.push_back(merged);
-    write_file(r, merged, r.merge_text);
+    if (!r.device_writers) write_file(r, merged, r.merge_text);
     r.merge_text.clear();
     r.output_counts.insert(r.output_counts.begin(), r.merged_count);  // output.rs:171 (the file name went to the back)
     r.merged_count = 0;
@@ -820,7 +860,35 @@ int main(int argc, char** argv) {
   const bool sample_group = bc_plan_has_sample(r.plan) != 0;
   for (const auto& s : r.samples) r.sample_keys.push_back(s.first);
   if (r.samples.empty() && !sample_group) r.sample_keys.push_back("barcode");
-  if (!multi && bc_engine_finish(r.engine, &n_rows)) die("%s", bc_last_error());
+  const bool dense = bc_plan_mode(r.plan) == 1;
+  // (an ID with a comma in it would split into other columns on the string path of enrichment: such plans keep it)
+  bool plain_ids = true, enrich_tried = false;  // enrich_tried: fill_enrichment has run (and, if it is not filled, failed)
+  for (const auto& set : r.counted)
+    for (const auto& kv : set) plain_ids = plain_ids && kv.second.find(',') == std::string::npos;
+  // Dense plans: the full-counts files are rendered on the device from the table (bc_engine_render_counts / _merged) and
+  // no row ever becomes a host string.  Kept on the rows: a run whose enrichment needs them (the string path), and a
+  // sample file next to a scheme without a sample group, whose "barcode" key exists only once a row lands on it
+  // (add_row below).
+  {
+    const char* dw = getenv("BC_DEVICE_WRITERS");
+    r.device_writers = dense && !(dw && strcmp(dw, "0") == 0) && r.counted.size() == r.barcode_num &&
+                       (sample_group || r.samples.empty());
+    if (r.device_writers && r.args.enrich) {
+      enrich_tried = plain_ids;
+      r.device_writers = plain_ids && fill_enrichment(r, sample_group);
+    }
+    if (r.device_writers) {
+      if (sample_group)
+        for (uint32_t i = 0; i < r.samples.size(); ++i) r.sample_index[r.samples[i].first] = i;
+      else
+        r.sample_index["barcode"] = 0;
+      n_rows = 0;  // (no row is read below)
+    }
+  }
+  if (getenv("BC_WRITERS_VERBOSE"))  // (which path writes the full-counts files; tests assert it)
+    fprintf(stderr, "[barcode-count] writers: %s\n",
+            r.device_writers ? "device text (bc_engine_render_counts)" : "per-row strings");
+  if (!multi && !r.device_writers && bc_engine_finish(r.engine, &n_rows)) die("%s", bc_last_error());
   r.counted_map.resize(r.counted.size());
   for (size_t b = 0; b < r.counted.size(); ++b)
     for (const auto& kv : r.counted[b]) r.counted_map[b][kv.first] = kv.second;
@@ -835,7 +903,9 @@ int main(int argc, char** argv) {
     it->second.push_back({code, written, cnt});
     if (r.args.merge_output) r.results_map[key][code] = cnt;
   };
-  if (bc_plan_mode(r.plan) == 1) {
+  if (r.device_writers) {
+    // nothing to rebuild: the writers read the table
+  } else if (dense) {
     // dense plan: rows come as indices into the known sets; the sequence / ID strings are looked up
     const uint32_t nb = r.barcode_num ? r.barcode_num : 1;
     const uint64_t block = 1u << 20;
@@ -866,13 +936,8 @@ int main(int argc, char** argv) {
       add_row(sample, tuple, r.counted.empty() ? std::string(tuple) : convert_code(r, tuple), cnt);
     }
   }
-  if (r.args.enrich && bc_plan_mode(r.plan) == 1 && r.counted.size() == r.barcode_num) {
-    // (an ID with a comma in it would split into other columns on the string path: such plans keep that path)
-    bool plain_ids = true;
-    for (const auto& set : r.counted)
-      for (const auto& kv : set) plain_ids = plain_ids && kv.second.find(',') == std::string::npos;
-    if (plain_ids) fill_enrichment(r, sample_group);
-  }
+  if (r.args.enrich && dense && r.counted.size() == r.barcode_num && plain_ids && !enrich_tried)
+    fill_enrichment(r, sample_group);
   if (r.args.enrich && getenv("BC_ENRICH_VERBOSE"))  // (which path built the Single / Double maps; tests assert it)
     fprintf(stderr, "[barcode-count] enrichment: %s\n",
             r.enrich_filled ? "device marginal sums (bc_engine_enrich)" : "per-row string adds");

@@ -21,6 +21,7 @@
 #include "../../include/barcode_count_hip.h"
 #include "bc_kernel.h"
 #include "bc_enrich.h"
+#include "bc_render.h"
 #include "bc_fold.h"
 #include "bc_jit.h"
 #include "bc_plan.hpp"
@@ -644,6 +645,12 @@ struct bc_engine {
   LongHost lh;
   LongPlan* d_long = nullptr;
   const bc_plan* src_plan = nullptr;  // (the caller keeps the plan alive for the engine's lifetime)
+  // the label pool of the text renderer (bc_render.h), built at the first render: the IDs of the counted sets
+  bool render_pool_ready = false;
+  uint32_t* d_label_off = nullptr;
+  uint8_t* d_label_bytes = nullptr;
+  uint32_t label_off_start[kMaxGroups] = {0};
+  uint32_t label_max[kMaxGroups] = {0};  // the longest ID of each counted set
   bool table_materialized = false;  // random-barcode plans: d_table holds the per-tuple distinct counts of the current
                                     // key set (bc_engine_materialize_table), possibly summed over ranks since
 };
@@ -1783,6 +1790,263 @@ int bc_engine_enrich(bc_engine* e, uint64_t* single_counts, uint64_t* double_cou
   if (n_double) HIP_TRY(hipMemcpyAsync(double_counts, d_double, n_double * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return BC_OK;
+}
+
+// ---- counts as text (bc_render.h / bc_render.hip) ----
+
+// The IDs of the counted sets on the device, once per engine: per group N_g + 1 offsets, and the bytes back to back.
+static int ensure_render_pool(bc_engine* e, const char* who) {
+  if (e->render_pool_ready) return BC_OK;
+  const uint32_t G = e->barcode_num;
+  std::vector<uint32_t> off;
+  std::string bytes;
+  try {
+    for (uint32_t g = 0; g < G; ++g) {
+      e->label_off_start[g] = (uint32_t)off.size();
+      e->label_max[g] = 0;
+      const uint32_t n = bc_plan_n_counted(e->src_plan, g);
+      for (uint32_t i = 0; i < n; ++i) {
+        const char* id = bc_plan_counted_id(e->src_plan, g, i);
+        const size_t len = id ? strlen(id) : 0;
+        if (bytes.size() + len > 0xFFFFFFF0ull || off.size() > 0xFFFFFFF0ull) {
+          set_error(std::string(who) + ": the IDs of the counted barcodes pass 4 GB");
+          return BC_ERR_UNSUPPORTED;
+        }
+        off.push_back((uint32_t)bytes.size());
+        if (len) bytes.append(id, len);
+        e->label_max[g] = std::max<uint32_t>(e->label_max[g], (uint32_t)len);
+      }
+      off.push_back((uint32_t)bytes.size());
+    }
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  // both parts in one allocation (offsets first: the bytes need no alignment), so a failure leaves nothing behind
+  const size_t off_bytes = off.size() * 4;
+  std::string image;
+  try {
+    image.assign((const char*)off.data(), off_bytes);
+    image += bytes;
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  void* d_pool = nullptr;
+  HIP_TRY(hipMalloc(&d_pool, image.size() ? image.size() : 16));
+  if (!image.empty()) {
+    const hipError_t hrc = hipMemcpy(d_pool, image.data(), image.size(), hipMemcpyHostToDevice);
+    if (hrc != hipSuccess) {
+      (void)hipFree(d_pool);
+      HIP_TRY(hrc);
+    }
+  }
+  try {
+    e->allocs.push_back(d_pool);
+  } catch (const std::bad_alloc&) {
+    (void)hipFree(d_pool);
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  e->d_label_off = (uint32_t*)d_pool;
+  e->d_label_bytes = (uint8_t*)d_pool + off_bytes;
+  e->render_pool_ready = true;
+  return BC_OK;
+}
+
+// The lines of the tuples for which some listed sample counts, in ascending tuple order, handed to `fn` in chunks that
+// end with a line.  Pass 1 sizes every block of the tuple space, the host scans the sizes and cuts the space into ranges
+// whose text fits one staging buffer, pass 2 writes range after range into one of two buffers (device + pinned) while
+// the host hands on the range before.  A block whose text passes the buffer is cut between its lines from their
+// lengths.  Device memory: 2 x buffer + 12 bytes per block of 1024 tuples.
+static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, void* user,
+                       uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (P.sparse) {
+    set_error(std::string(who) + ": the plan keeps raw captures, whose rows are sequences, not indices: write them from "
+              "bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (!fn || (n_cols && !cols)) {
+    set_error(std::string(who) + ": null callback or sample list");
+    return BC_ERR_INVALID;
+  }
+  static_assert(bc::kRenderMaxG >= kMaxGroups, "a plan's counted barcodes fit the view");
+  bc::RenderView v;
+  memset(&v, 0, sizeof v);
+  v.G = e->barcode_num;
+  v.T = 1;
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    v.n[g] = P.groups[g0 + g].n_refs;
+    v.T *= v.n[g];
+  }
+  const uint64_t S = v.T ? e->table_entries / v.T : 0;
+  for (uint32_t c = 0; c < n_cols; ++c)
+    if (cols[c] >= S) {
+      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
+      return BC_ERR_INVALID;
+    }
+  int rc = dense_counts_ready(e);
+  if (rc) return rc;
+  if (n_cols == 0 || v.T == 0 || e->table_entries == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    if (bc_plan_n_counted(e->src_plan, g) != v.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
+      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+      return BC_ERR_STATE;
+    }
+    v.off_start[g] = e->label_off_start[g];
+    max_line += e->label_max[g];
+  }
+  if (max_line > bc::kRenderMaxLine) {
+    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
+              std::to_string(bc::kRenderMaxLine));
+    return BC_ERR_UNSUPPORTED;
+  }
+  uint64_t cap = 64ull << 20;
+  if (const char* ev = getenv("BC_RENDER_CHUNK_BYTES")) {  // (a value that does not parse, or 0, leaves the default)
+    char* end = nullptr;
+    const unsigned long long x = strtoull(ev, &end, 0);
+    if (end != ev && *end == '\0' && x > 0) cap = x;
+  }
+  cap = std::max(cap, max_line);  // never smaller than the longest possible line: every line fits some chunk
+
+  HIP_TRY(hipSetDevice(e->device));
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
+  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
+  v.table = e->d_table;
+  v.bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
+  v.cols = d_cols;
+  v.n_cols = n_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+
+  const uint64_t n_blocks = (v.T + kRenderBlock - 1) / kRenderBlock;
+  uint32_t* d_rows = nullptr;
+  unsigned long long* d_bytes = nullptr;
+  HIP_TRY(g.dmalloc(&d_rows, n_blocks * 4));
+  HIP_TRY(g.dmalloc(&d_bytes, (n_blocks + 1) * 8));
+  HIP_TRY(hipMemsetAsync(d_rows, 0, n_blocks * 4, e->stream));
+  HIP_TRY(hipMemsetAsync(d_bytes, 0, (n_blocks + 1) * 8, e->stream));
+  HIP_TRY(bc_render_sizes_launch(v, n_blocks, d_rows, d_bytes, e->stream));
+  std::vector<uint32_t> rows;
+  std::vector<unsigned long long> prefix;
+  try {
+    rows.resize(n_blocks);
+    prefix.resize(n_blocks + 1);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  HIP_TRY(hipMemcpyAsync(rows.data(), d_rows, n_blocks * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(prefix.data(), d_bytes, n_blocks * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  uint64_t total_rows = 0, total_bytes = 0;
+  for (uint64_t b = 0; b < n_blocks; ++b) {  // sizes -> exclusive scan, in place
+    const uint64_t x = prefix[b];
+    prefix[b] = total_bytes;
+    total_bytes += x;
+    total_rows += rows[b];
+  }
+  prefix[n_blocks] = total_bytes;
+  if (total_rows == 0) return BC_OK;
+  HIP_TRY(hipMemcpyAsync(d_bytes, prefix.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, e->stream));
+
+  const uint64_t slot = std::min(cap, total_bytes);
+  const size_t slot_alloc = (size_t)((slot + 3) & ~3ull);
+  uint8_t* d_text[2] = {nullptr, nullptr};
+  uint8_t* h_text[2] = {nullptr, nullptr};
+  hipEvent_t landed[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; ++k) {
+    HIP_TRY(g.dmalloc(&d_text[k], slot_alloc));
+    HIP_TRY(g.hmalloc(&h_text[k], slot_alloc));
+    HIP_TRY(g.event(&landed[k]));
+    if (total_bytes <= cap) break;  // one range: one slot
+  }
+  uint32_t *d_len = nullptr, *h_len = nullptr;  // a block's line lengths, when one has to be cut inside
+  uint64_t pending[2] = {0, 0};
+  auto consume = [&](int k) -> int {
+    HIP_TRY(hipEventSynchronize(landed[k]));
+    if (pending[k] && fn((const char*)h_text[k], (size_t)pending[k], user) != 0) {
+      set_error(std::string(who) + ": stopped by the callback");
+      return BC_ERR_STATE;
+    }
+    return BC_OK;
+  };
+  int64_t seg = 0;
+  // one range: the lines of tuples [lo, hi) inside blocks [b0, b1), `bytes` of text that starts at scan position `sub`
+  auto emit = [&](uint64_t b0, uint64_t b1, uint64_t lo, uint64_t hi, uint64_t sub, uint64_t bytes) -> int {
+    const int k = (int)(seg & 1);
+    if (bytes) {
+      HIP_TRY(bc_render_write_launch(v, b0, b1 - b0, lo, hi, d_rows, d_bytes, sub, d_text[k], slot, e->stream));
+      HIP_TRY(hipMemcpyAsync(h_text[k], d_text[k], bytes, hipMemcpyDeviceToHost, e->stream));
+    }
+    pending[k] = bytes;
+    HIP_TRY(hipEventRecord(landed[k], e->stream));
+    int r2 = BC_OK;
+    if (seg >= 1) r2 = consume(k ^ 1);
+    ++seg;
+    return r2;
+  };
+  auto run = [&]() -> int {
+    uint64_t b0 = 0;
+    while (b0 < n_blocks) {
+      uint64_t b1 = b0;
+      while (b1 < n_blocks && prefix[b1 + 1] - prefix[b0] <= slot) ++b1;
+      int r2;
+      if (b1 > b0) {
+        if (prefix[b1] == prefix[b0]) {  // (nothing but empty blocks)
+          b0 = b1;
+          continue;
+        }
+        r2 = emit(b0, b1, b0 * kRenderBlock, std::min<uint64_t>(v.T, b1 * kRenderBlock), prefix[b0], prefix[b1] - prefix[b0]);
+        if (r2 != BC_OK) return r2;
+        b0 = b1;
+        continue;
+      }
+      // block b0 alone passes the buffer: cut it between its lines
+      if (!d_len) {
+        HIP_TRY(g.dmalloc(&d_len, kRenderBlock * 4));
+        HIP_TRY(g.hmalloc(&h_len, kRenderBlock * 4));
+      }
+      const uint64_t t0 = b0 * kRenderBlock;
+      const uint32_t n = (uint32_t)std::min<uint64_t>(kRenderBlock, v.T - t0);
+      HIP_TRY(bc_render_lens_launch(v, t0, n, d_len, e->stream));
+      HIP_TRY(hipMemcpyAsync(h_len, d_len, n * 4, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      uint32_t len[kRenderBlock];  // (a copy: h_len is reused by a later block while ranges are in flight)
+      memcpy(len, h_len, n * 4);
+      uint32_t i = 0;
+      while (i < n) {
+        uint64_t bytes = 0;
+        uint32_t j = i;
+        while (j < n && bytes + len[j] <= slot) bytes += len[j++];  // (a line always fits: slot >= max_line)
+        if (bytes && (r2 = emit(b0, b0 + 1, t0 + i, t0 + j, prefix[b0], bytes)) != BC_OK) return r2;
+        i = j;
+      }
+      ++b0;
+    }
+    return seg ? consume((int)((seg - 1) & 1)) : BC_OK;
+  };
+  rc = run();
+  (void)hipStreamSynchronize(e->stream);  // nothing of ours may still be writing the staging buffers when they go
+  if (rc == BC_OK && n_rows) *n_rows = total_rows;
+  return rc;
+}
+
+int bc_engine_render_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_text(e, "bc_engine_render_counts", &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
+                            uint64_t* n_rows) {
+  return render_text(e, "bc_engine_render_merged", sample_idx, n_samples, fn, user, n_rows);
 }
 
 // Random-barcode plans with a dense table: the count of a tuple is the number of distinct random barcodes seen with it
