@@ -215,6 +215,39 @@ int bc_engine_render_counts(bc_engine *e, uint32_t sample_idx, bc_text_fn fn, vo
 int bc_engine_render_merged(bc_engine *e, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn, void *user,
                             uint64_t *n_rows);
 
+/* The Single and Double enrichment files of a dense plan as CSV text, written on the device from the sums
+ * bc_engine_enrich computes (same notation: G, N_g, SUM, P, off_g, poff), with the preamble, the chunking and the callback
+ * contract of bc_engine_render_counts / _merged (BC_RENDER_CHUNK_BYTES, two staging buffers, `fn` != 0 -> BC_ERR_STATE
+ * with the engine still usable, BC_ERR_NOMEM likewise; the table, the counters and the rows stay as they are; no header).
+ * A key is an index k into one sample's slice of the sums; lines come in ascending k:
+ *   BC_ENRICH_SINGLE: k in [0, SUM) = off_g + i_g;  BC_ENRICH_DOUBLE: k in [0, P) = poff_(g,h) + i_g * N_h + i_h (none
+ *   for G < 3: zero lines, BC_OK).
+ * A line has G fields joined by commas, as add_single / add_double build the key (info.rs:840-904): field g (and h)
+ * holds the ID, copied byte for byte, every other field is empty; then the count(s), u64 in decimal.  G = 3, g = 1:
+ *   ,id,,count\n
+ *   bc_engine_render_enriched: one line per key whose sum for sample_idx is not zero.
+ *   bc_engine_render_enriched_merged: one line per key whose sum is not zero for some LISTED sample, one count per
+ *     listed sample (any order, a sample may come twice), 0 written as "0".
+ * Entries of one known set whose IDs are byte-equal are ONE key (the reference's maps are keyed by text): their sums are
+ * folded, on the device, into the entry with the smallest index, and only that entry has a line.  Text that coincides
+ * across DIFFERENT groups or pairs -- possible only when some ID is empty -- is NOT merged: write such plans from
+ * bc_engine_enrich on the host.
+ * The sums are computed once (one pass over the table) and kept on the device, S * (SUM + P) * 8 bytes, until
+ * something changes what bc_engine_finish would hand out: a submit, a reset, a key or count import, bc_engine_clear_keys,
+ * bc_engine_materialize_table, the exchange of bc_engine_finish_all.  A table the caller owns or has taken the pointer
+ * of (bc_engine_table_ptr) may change unseen: its sums are computed anew for every call.  bc_engine_enrich is not
+ * affected: it returns the raw, unfolded sums from scratch of its own.
+ * Plans that keep raw captures: BC_ERR_UNSUPPORTED; another kind, or a sample index out of range: BC_ERR_INVALID. */
+#define BC_ENRICH_SINGLE 1
+#define BC_ENRICH_DOUBLE 2
+/* How many times the engine has computed those sums (one pass over the table each) since it was created: the renders of
+ * one state of the counts make one pass between them; every render of a table the caller can write makes its own.
+ * Read-only: does not wait for the device. */
+int bc_engine_enrich_render_passes(const bc_engine *e, uint64_t *n);
+int bc_engine_render_enriched(bc_engine *e, int kind, uint32_t sample_idx, bc_text_fn fn, void *user, uint64_t *n_rows);
+int bc_engine_render_enriched_merged(bc_engine *e, int kind, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn,
+                                     void *user, uint64_t *n_rows);
+
 /* Row i as the reference's Results holds it (info.rs:661-665): the sample key (a sample barcode
  * sequence, or "barcode" without a sample group) and the counted barcodes "b1,b2,.." as sequences.
  * Works for every plan, including those that keep raw captures (no sample / counted-barcode

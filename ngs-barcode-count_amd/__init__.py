@@ -17,9 +17,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import COUNTER_NAMES, SynthParams
+from ._lib import BC_ENRICH_SINGLE as ENRICH_SINGLE, BC_ENRICH_DOUBLE as ENRICH_DOUBLE
 
 __all__ = ["Plan", "Engine", "Comm", "Synth", "SequenceFormat", "BarcodeConversions", "MaxSeqErrors", "SequenceErrors",
-           "Results", "ResultsEnrichment", "SequenceParser", "fix_error", "BarcodeCountError", "COUNTER_NAMES"]
+           "Results", "ResultsEnrichment", "SequenceParser", "fix_error", "BarcodeCountError", "COUNTER_NAMES",
+           "ENRICH_SINGLE", "ENRICH_DOUBLE"]
 
 
 class BarcodeCountError(RuntimeError):
@@ -238,6 +240,12 @@ class Engine:
         _check(self._lib, self._lib.bc_engine_count_log_folds(self._e, C.byref(n)))
         return n.value
 
+    def enrich_render_passes(self):
+        """table passes made for the sums behind render_enriched() / render_enriched_merged() since the engine was created"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_enrich_render_passes(self._e, C.byref(n)))
+        return n.value
+
     def gz_blocks_inflated(self):
         """BGZF blocks inflated on the device for this engine since it was created (0: every .gz went through zlib)"""
         n = C.c_uint64()
@@ -325,6 +333,21 @@ class Engine:
         cols = np.ascontiguousarray(list(samples), dtype=np.uint32)
         return self._render(lambda fn, n: self._lib.bc_engine_render_merged(
             self._e, cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
+
+    def render_enriched(self, kind, sample=0, on_text=None):
+        """bc_engine_render_enriched: the lines of sample index `sample`'s Single (kind = ENRICH_SINGLE) or Double
+        (ENRICH_DOUBLE) file (no header), written on the device in ascending key order: G comma-joined fields of which
+        one (two) holds an ID, then the count, e.g. b",id,,count\\n".  IDs shared inside a set are one key.  Returns as
+        render_counts does."""
+        return self._render(lambda fn, n: self._lib.bc_engine_render_enriched(self._e, int(kind), int(sample), fn, None, n),
+                            on_text)
+
+    def render_enriched_merged(self, kind, samples, on_text=None):
+        """bc_engine_render_enriched_merged: the merged Single / Double file's lines (no header) for the sample indices
+        `samples` as columns, in that order: one line per key that counts in any LISTED sample."""
+        cols = np.ascontiguousarray(list(samples), dtype=np.uint32)
+        return self._render(lambda fn, n: self._lib.bc_engine_render_enriched_merged(
+            self._e, int(kind), cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
 
     def enrichment(self, doubles=True):
         """bc_engine_enrich: single and pair counts of the counts finish() would hand out now, summed on the device ->

@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(CSRC_DIR, "libbarcode_count_hip.so")
 BC_OK = 0
 BC_ERR_INVALID, BC_ERR_UNSUPPORTED, BC_ERR_HIP, BC_ERR_NOMEM, BC_ERR_STATE, BC_ERR_COMM = -1, -2, -3, -4, -5, -6
 BC_COMM_ID_BYTES = 128
+BC_ENRICH_SINGLE, BC_ENRICH_DOUBLE = 1, 2  # `kind` of bc_engine_render_enriched
 COUNTER_NAMES = ["matched", "constant_region", "sample_barcode", "barcode", "duplicates", "low_quality",
                  "total_reads", "unsupported_reads"]
 
@@ -94,6 +95,8 @@ ENGINE_API = {
     "bc_engine_enrich": (_int, [_vp, _vp, _vp]),
     "bc_engine_render_counts": (_int, [_vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "bc_engine_render_merged": (_int, [_vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_render_enriched": (_int, [_vp, _int, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_render_enriched_merged": (_int, [_vp, _int, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "bc_engine_timing": (_int, [_vp, _int]),
     "bc_engine_kernel_ms": (_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "bc_engine_kernel_ms_each": (_int, [_vp, C.POINTER(C.c_double), _u64, C.POINTER(C.c_uint64)]),
@@ -101,6 +104,7 @@ ENGINE_API = {
     "bc_table_sum_u8": (_int, [_vp, _u32, _u64, _vp, _int, _vp]),
     "bc_engine_kernel_name": (_cp, [_vp]),
     "bc_engine_count_log_folds": (_int, [_vp, C.POINTER(C.c_uint64)]),
+    "bc_engine_enrich_render_passes": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_engine_sclk_mhz": (_int, [_vp, C.POINTER(C.c_double)]),
     "bc_plan_precompile": (_int, [_vp, _u32, _u32, _int, _cp]),  # lives with the engine: it drives the device compiler
     "bc_engine_trace": (_int, [_vp, _vp, _vp]),

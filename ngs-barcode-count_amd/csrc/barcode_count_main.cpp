@@ -281,6 +281,8 @@ struct Run {
   std::string merge_text, sample_text;
   // the full-counts files as text from the device (bc_engine_render_counts / _merged): no rows on the host at all
   bool device_writers = false;
+  // ... and the Single / Double files (bc_engine_render_enriched / _merged): no single_hash / double_hash at all
+  bool device_enrich = false;
   std::unordered_map<std::string, uint32_t> sample_index;  // sample key -> the engine's sample index
 };
 
@@ -535,7 +537,68 @@ void merged_header(Run& r, const std::vector<std::string>& samples, const std::s
   r.merge_text += h + "\n";
 }
 
+// The device path of a counts file: the header, then the text chunks as they leave the device.  stdout gets what
+// add_counts_string prints for that many rows (its lines depend on the row count alone).
+int text_to_file(const char* text, size_t n, void* user) { return fwrite(text, 1, n, (FILE*)user) == n ? 0 : 1; }
+// enriched: 0 for a full-counts file, else BC_ENRICH_SINGLE / BC_ENRICH_DOUBLE
+uint64_t render_file(Run& r, const std::string& name, const std::string& head, const std::vector<uint32_t>& cols, bool merged,
+                     int enriched = 0) {
+  std::string path = r.args.output_dir;
+  if (!path.empty() && path.back() != '/') path.push_back('/');
+  path += name;
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) die("cannot create %s", path.c_str());
+  if (fwrite(head.data(), 1, head.size(), f) != head.size()) die("%s: write failed", path.c_str());
+  uint64_t n = 0;
+  int rc;
+  if (enriched)
+    rc = merged ? bc_engine_render_enriched_merged(r.engine, enriched, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
+                : bc_engine_render_enriched(r.engine, enriched, cols[0], text_to_file, f, &n);
+  else
+    rc = merged ? bc_engine_render_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
+                : bc_engine_render_counts(r.engine, cols[0], text_to_file, f, &n);
+  if (rc != BC_OK) die("%s: %s", path.c_str(), ferror(f) ? "write failed" : bc_last_error());
+  if (fclose(f) != 0) die("%s: write failed", path.c_str());
+  return n;
+}
+// what add_counts_string prints while it walks n rows: a line every 50,000 rows, and the total
+void print_rows_progress(uint64_t n) {
+  for (uint64_t k = 50000; k <= n; k += 50000) printf("Barcodes counted: %s\r", commas(k).c_str());
+  printf("Barcodes counted: %s\r\n", commas(n).c_str());
+}
+// The device path of the Single / Double files: a key is an index into the device's marginal sums, its line a function
+// of that index (bc_engine_render_enriched).  Every sample key has a file, as every key has a map on the host path
+// (add_sample_barcodes); file names, headers, stdout and output_counts are those of write_enriched_files below.
+void render_enriched_files(Run& r, Enriched type) {
+  const auto samples = ordered_samples(r, r.sample_keys);
+  const char* descriptor = type == kSingle ? "Single" : "Double";
+  const int kind = type == kSingle ? BC_ENRICH_SINGLE : BC_ENRICH_DOUBLE;
+  std::string header = create_header(r);
+  if (r.args.merge_output) merged_header(r, samples, header);
+  header += ",Count\n";
+  for (const auto& sb : samples) {
+    const std::string file_name = r.args.prefix + "_" + sample_name(r, sb) + "_counts." + descriptor + ".csv";
+    printf("%s\n", file_name.c_str());
+    r.output_files.push_back(file_name);
+    const uint64_t count = render_file(r, file_name, header, {r.sample_index.at(sb)}, false, kind);
+    print_rows_progress(count);
+    r.output_counts.push_back(count);
+  }
+  if (r.args.merge_output) {
+    const std::string merged = r.args.prefix + "_counts.all." + descriptor + ".csv";
+    printf("%s\n", merged.c_str());
+    r.output_files.push_back(merged);
+    std::vector<uint32_t> cols;
+    for (const auto& sb : samples) cols.push_back(r.sample_index.at(sb));
+    const uint64_t merged_count = render_file(r, merged, r.merge_text, cols, true, kind);
+    printf("Barcodes counted: %s\n", commas(merged_count).c_str());
+    r.merge_text.clear();
+    r.output_counts.insert(r.output_counts.end() - (long)samples.size(), merged_count);  // output.rs:478-481
+  }
+}
+
 void write_enriched_files(Run& r, Enriched type) {  // output.rs:364-485
+  if (r.device_enrich) return render_enriched_files(r, type);
   auto& hash = type == kSingle ? r.single_hash : r.double_hash;
   std::vector<std::string> keys;
   for (const auto& k : r.sample_keys)
@@ -567,28 +630,6 @@ void write_enriched_files(Run& r, Enriched type) {  // output.rs:364-485
   }
 }
 
-// The device path of a full-counts file: the header, then the text chunks as they leave the device.  stdout gets what
-// add_counts_string prints for that many rows (its lines depend on the row count alone).
-int text_to_file(const char* text, size_t n, void* user) { return fwrite(text, 1, n, (FILE*)user) == n ? 0 : 1; }
-uint64_t render_file(Run& r, const std::string& name, const std::string& head, const std::vector<uint32_t>& cols, bool merged) {
-  std::string path = r.args.output_dir;
-  if (!path.empty() && path.back() != '/') path.push_back('/');
-  path += name;
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) die("cannot create %s", path.c_str());
-  if (fwrite(head.data(), 1, head.size(), f) != head.size()) die("%s: write failed", path.c_str());
-  uint64_t n = 0;
-  const int rc = merged ? bc_engine_render_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
-                        : bc_engine_render_counts(r.engine, cols[0], text_to_file, f, &n);
-  if (rc != BC_OK) die("%s: %s", path.c_str(), ferror(f) ? "write failed" : bc_last_error());
-  if (fclose(f) != 0) die("%s: write failed", path.c_str());
-  return n;
-}
-// what add_counts_string prints while it walks n rows: a line every 50,000 rows, and the total
-void print_rows_progress(uint64_t n) {
-  for (uint64_t k = 50000; k <= n; k += 50000) printf("Barcodes counted: %s\r", commas(k).c_str());
-  printf("Barcodes counted: %s\r\n", commas(n).c_str());
-}
 uint64_t render_sample_file(Run& r, const std::string& sample, const std::string& name, const std::string& head) {
   const uint64_t n = render_file(r, name, head, {r.sample_index.at(sample)}, false);
   print_rows_progress(n);
@@ -597,7 +638,7 @@ uint64_t render_sample_file(Run& r, const std::string& sample, const std::string
 
 void write_counts_files(Run& r) {  // output.rs:74-181
   auto samples = ordered_samples(r, r.sample_keys);
-  if (r.args.enrich)
+  if (r.args.enrich && !r.device_enrich)
     for (const auto& k : samples) {  // ResultsEnrichment::add_sample_barcodes, info.rs:829-837
       r.single_hash[k];
       r.double_hash[k];
@@ -863,8 +904,12 @@ int main(int argc, char** argv) {
   const bool dense = bc_plan_mode(r.plan) == 1;
   // (an ID with a comma in it would split into other columns on the string path of enrichment: such plans keep it)
   bool plain_ids = true, enrich_tried = false;  // enrich_tried: fill_enrichment has run (and, if it is not filled, failed)
+  bool no_empty_id = true;
   for (const auto& set : r.counted)
-    for (const auto& kv : set) plain_ids = plain_ids && kv.second.find(',') == std::string::npos;
+    for (const auto& kv : set) {
+      plain_ids = plain_ids && kv.second.find(',') == std::string::npos;
+      no_empty_id = no_empty_id && !kv.second.empty();
+    }
   // Dense plans: the full-counts files are rendered on the device from the table (bc_engine_render_counts / _merged) and
   // no row ever becomes a host string.  Kept on the rows: a run whose enrichment needs them (the string path), and a
   // sample file next to a scheme without a sample group, whose "barcode" key exists only once a row lands on it
@@ -874,8 +919,16 @@ int main(int argc, char** argv) {
     r.device_writers = dense && !(dw && strcmp(dw, "0") == 0) && r.counted.size() == r.barcode_num &&
                        (sample_group || r.samples.empty());
     if (r.device_writers && r.args.enrich) {
-      enrich_tried = plain_ids;
-      r.device_writers = plain_ids && fill_enrichment(r, sample_group);
+      // The Single / Double files too, unless an ID is empty: ",," is then the text of keys in different groups, which
+      // the reference's maps add up and the device's key space keeps apart.
+      const char* de = getenv("BC_DEVICE_ENRICH_WRITERS");
+      uint64_t n_single = 0, n_double = 0;
+      r.device_enrich = plain_ids && no_empty_id && !(de && strcmp(de, "0") == 0) &&
+                        bc_engine_enrich_entries(r.engine, &n_single, &n_double) == BC_OK;
+      if (!r.device_enrich) {
+        enrich_tried = plain_ids;
+        r.device_writers = plain_ids && fill_enrichment(r, sample_group);
+      }
     }
     if (r.device_writers) {
       if (sample_group)
@@ -888,6 +941,9 @@ int main(int argc, char** argv) {
   if (getenv("BC_WRITERS_VERBOSE"))  // (which path writes the full-counts files; tests assert it)
     fprintf(stderr, "[barcode-count] writers: %s\n",
             r.device_writers ? "device text (bc_engine_render_counts)" : "per-row strings");
+  if (r.args.enrich && getenv("BC_WRITERS_VERBOSE"))  // (... and the Single / Double files)
+    fprintf(stderr, "[barcode-count] enrichment writers: %s\n",
+            r.device_enrich ? "device text (bc_engine_render_enriched)" : "per-row strings");
   if (!multi && !r.device_writers && bc_engine_finish(r.engine, &n_rows)) die("%s", bc_last_error());
   r.counted_map.resize(r.counted.size());
   for (size_t b = 0; b < r.counted.size(); ++b)
@@ -936,12 +992,19 @@ int main(int argc, char** argv) {
       add_row(sample, tuple, r.counted.empty() ? std::string(tuple) : convert_code(r, tuple), cnt);
     }
   }
-  if (r.args.enrich && dense && r.counted.size() == r.barcode_num && plain_ids && !enrich_tried)
+  if (r.args.enrich && !r.device_enrich && dense && r.counted.size() == r.barcode_num && plain_ids && !enrich_tried)
     fill_enrichment(r, sample_group);
   if (r.args.enrich && getenv("BC_ENRICH_VERBOSE"))  // (which path built the Single / Double maps; tests assert it)
     fprintf(stderr, "[barcode-count] enrichment: %s\n",
-            r.enrich_filled ? "device marginal sums (bc_engine_enrich)" : "per-row string adds");
+            r.device_enrich ? "device marginal sums (bc_engine_render_enriched)"
+                            : (r.enrich_filled ? "device marginal sums (bc_engine_enrich)" : "per-row string adds"));
   write_counts_files(r);
+  if (r.args.enrich && getenv("BC_ENRICH_VERBOSE")) {  // (the device path of the Single / Double files builds none)
+    size_t keys = 0;
+    for (const auto* maps : {&r.single_hash, &r.double_hash})
+      for (const auto& kv : *maps) keys += kv.second.size();
+    fprintf(stderr, "[barcode-count] enrichment maps: %zu keys on the host\n", keys);
+  }
   write_stats_file(r, start, start_ms, counters, total_reads);
   printf("\nTotal time: %s\n", elapsed_text(now_ms() - start_ms).c_str());  // main.rs:156-164
   bc_engine_destroy(r.engine);

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <functional>
 #include <thread>
+#include <unordered_map>
 #include <string>
 #include <vector>
 
@@ -22,6 +23,7 @@
 #include "bc_kernel.h"
 #include "bc_enrich.h"
 #include "bc_render.h"
+#include "bc_enrich_render.h"
 #include "bc_fold.h"
 #include "bc_jit.h"
 #include "bc_plan.hpp"
@@ -653,7 +655,17 @@ struct bc_engine {
   uint32_t label_max[kMaxGroups] = {0};  // the longest ID of each counted set
   bool table_materialized = false;  // random-barcode plans: d_table holds the per-tuple distinct counts of the current
                                     // key set (bc_engine_materialize_table), possibly summed over ranks since
+  // The enrichment renderer (bc_enrich_render.h).  counts_epoch moves whenever what bc_engine_finish would hand out may
+  // have changed (counts_changed()); the folded sums on the device are those of epoch sums_epoch and are served only
+  // while the two agree -- and never for a table somebody else may write (caller-owned, or its pointer handed out).
+  uint64_t counts_epoch = 1, sums_epoch = 0;
+  unsigned long long* d_sums = nullptr;  // S * SUM singles, then S * P doubles
+  uint64_t sums_passes = 0;              // table passes made for them since the engine was created
+  bool canon_ready = false;              // the canonical maps of the label pool have been built
+  uint32_t* d_canon = nullptr;           // canon[off_g + i]; NULL when no set shares an ID
 };
+
+static void counts_changed(bc_engine* e) { ++e->counts_epoch; }
 
 static int upload(bc_engine* e, const void* src, size_t bytes, uint64_t* out) {
   void* d = nullptr;
@@ -687,6 +699,7 @@ static void engine_free(bc_engine* e) {
   if (e->d_slots) (void)hipFree(e->d_slots);
   if (e->d_vals) (void)hipFree(e->d_vals);
   if (e->d_ready) (void)hipFree(e->d_ready);
+  if (e->d_sums) (void)hipFree(e->d_sums);
   if (e->d_counters) (void)hipFree(e->d_counters);
   if (e->d_plan) (void)hipFree(e->d_plan);
   if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
@@ -1123,6 +1136,7 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
   const uint32_t nd = (maxlen + 3) / 4;
   HIP_TRY(hipSetDevice(e->device));
   e->table_materialized = false;
+  counts_changed(e);
   {
     const int rc = set_reserve(e, n_reads);
     if (rc != BC_OK) return rc;
@@ -1310,6 +1324,7 @@ int bc_engine_reset(bc_engine* e) { return reset_impl(e, true); }
 int bc_engine_reset_results(bc_engine* e) { return reset_impl(e, false); }
 static int reset_impl(bc_engine* e, bool counters_too) {
   HIP_TRY(hipSetDevice(e->device));
+  counts_changed(e);
   const uint64_t dirty_off = e->h.plan.dirty_off;
   if (e->d_bits && dirty_off && !e->table_all_dirty) {
     // two-level counting: after a short job the table is almost all zeros -- first occurrences live in the bit map --
@@ -1361,6 +1376,7 @@ void* bc_engine_table_ptr(bc_engine* e) {
 void* bc_internal_table_folded(bc_engine* e) {
   if (e->bits_dirty && hipSetDevice(e->device) == hipSuccess && fold_bits(e) == BC_OK) (void)hipStreamSynchronize(e->stream);
   e->table_all_dirty = true;
+  counts_changed(e);
   return e->d_table;
 }
 // ... or as it stands, with the bit map beside it (*bits: NULL when nothing is pending there): the exchange packs
@@ -1368,9 +1384,11 @@ void* bc_internal_table_folded(bc_engine* e) {
 void* bc_internal_table_unfolded(bc_engine* e, const void** bits) {
   *bits = e->bits_dirty ? e->d_bits : nullptr;
   e->table_all_dirty = true;
+  counts_changed(e);
   return e->d_table;
 }
 int bc_internal_table_now_plain(bc_engine* e) {
+  counts_changed(e);  // (the exchange has written the job's sum into the table)
   if (e->d_bits) HIP_TRY(hipMemsetAsync(e->d_bits, 0, e->n_bit_words * 4, e->stream));
   e->bits_dirty = false;
   e->reads_since_fold = 0;
@@ -1855,58 +1873,41 @@ static int ensure_render_pool(bc_engine* e, const char* who) {
   return BC_OK;
 }
 
-// The lines of the tuples for which some listed sample counts, in ascending tuple order, handed to `fn` in chunks that
-// end with a line.  Pass 1 sizes every block of the tuple space, the host scans the sizes and cuts the space into ranges
-// whose text fits one staging buffer, pass 2 writes range after range into one of two buffers (device + pinned) while
-// the host hands on the range before.  A block whose text passes the buffer is cut between its lines from their
-// lengths.  Device memory: 2 x buffer + 12 bytes per block of 1024 tuples.
-static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, void* user,
+}  // extern "C"  (overloads and a template: C++ linkage)
+
+// The three passes of a text render (bc_text_kernels.h) for either view, enqueued on `st`.
+static hipError_t text_sizes(const bc::RenderView& v, uint64_t nb, uint32_t* d_rows, unsigned long long* d_bytes, hipStream_t st) {
+  return bc_render_sizes_launch(v, nb, d_rows, d_bytes, st);
+}
+static hipError_t text_sizes(const bc::EnrichRenderView& v, uint64_t nb, uint32_t* d_rows, unsigned long long* d_bytes,
+                             hipStream_t st) {
+  return bc_enrich_render_sizes_launch(v, nb, d_rows, d_bytes, st);
+}
+static hipError_t text_lens(const bc::RenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t st) {
+  return bc_render_lens_launch(v, lo, n, d_len, st);
+}
+static hipError_t text_lens(const bc::EnrichRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t st) {
+  return bc_enrich_render_lens_launch(v, lo, n, d_len, st);
+}
+static hipError_t text_write(const bc::RenderView& v, uint64_t b0, uint64_t nb, uint64_t lo, uint64_t hi, const uint32_t* d_rows,
+                             const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out, uint64_t out_cap, hipStream_t st) {
+  return bc_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
+}
+static hipError_t text_write(const bc::EnrichRenderView& v, uint64_t b0, uint64_t nb, uint64_t lo, uint64_t hi,
+                             const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
+                             uint64_t out_cap, hipStream_t st) {
+  return bc_enrich_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
+}
+
+// The lines of the keys [0, n_keys) that have one, in ascending key order, handed to `fn` in chunks that end with a
+// line.  Pass 1 sizes every block of the key space, the host scans the sizes and cuts the space into ranges whose text
+// fits one staging buffer, pass 2 writes range after range into one of two buffers (device + pinned) while the host hands
+// on the range before.  A block whose text passes the buffer is cut between its lines from their lengths.  Device
+// memory: 2 x buffer + 12 bytes per block of 1024 keys.  max_line: no line is longer.
+template <class View>
+static int stream_text(bc_engine* e, const char* who, const View& v, uint64_t max_line, bc_text_fn fn, void* user,
                        uint64_t* n_rows) {
-  if (n_rows) *n_rows = 0;
-  const DevPlan& P = e->h.plan;
-  if (P.sparse) {
-    set_error(std::string(who) + ": the plan keeps raw captures, whose rows are sequences, not indices: write them from "
-              "bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (!fn || (n_cols && !cols)) {
-    set_error(std::string(who) + ": null callback or sample list");
-    return BC_ERR_INVALID;
-  }
-  static_assert(bc::kRenderMaxG >= kMaxGroups, "a plan's counted barcodes fit the view");
-  bc::RenderView v;
-  memset(&v, 0, sizeof v);
-  v.G = e->barcode_num;
-  v.T = 1;
-  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    v.n[g] = P.groups[g0 + g].n_refs;
-    v.T *= v.n[g];
-  }
-  const uint64_t S = v.T ? e->table_entries / v.T : 0;
-  for (uint32_t c = 0; c < n_cols; ++c)
-    if (cols[c] >= S) {
-      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
-      return BC_ERR_INVALID;
-    }
-  int rc = dense_counts_ready(e);
-  if (rc) return rc;
-  if (n_cols == 0 || v.T == 0 || e->table_entries == 0) return BC_OK;
-  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    if (bc_plan_n_counted(e->src_plan, g) != v.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
-      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-      return BC_ERR_STATE;
-    }
-    v.off_start[g] = e->label_off_start[g];
-    max_line += e->label_max[g];
-  }
-  if (max_line > bc::kRenderMaxLine) {
-    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
-              std::to_string(bc::kRenderMaxLine));
-    return BC_ERR_UNSUPPORTED;
-  }
+  const uint64_t n_keys = bc::text_keys(v);
   uint64_t cap = 64ull << 20;
   if (const char* ev = getenv("BC_RENDER_CHUNK_BYTES")) {  // (a value that does not parse, or 0, leaves the default)
     char* end = nullptr;
@@ -1915,26 +1916,15 @@ static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint
   }
   cap = std::max(cap, max_line);  // never smaller than the longest possible line: every line fits some chunk
 
-  HIP_TRY(hipSetDevice(e->device));
   ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
-  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
-  v.table = e->d_table;
-  v.bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
-  v.cols = d_cols;
-  v.n_cols = n_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-
-  const uint64_t n_blocks = (v.T + kRenderBlock - 1) / kRenderBlock;
+  const uint64_t n_blocks = (n_keys + kRenderBlock - 1) / kRenderBlock;
   uint32_t* d_rows = nullptr;
   unsigned long long* d_bytes = nullptr;
   HIP_TRY(g.dmalloc(&d_rows, n_blocks * 4));
   HIP_TRY(g.dmalloc(&d_bytes, (n_blocks + 1) * 8));
   HIP_TRY(hipMemsetAsync(d_rows, 0, n_blocks * 4, e->stream));
   HIP_TRY(hipMemsetAsync(d_bytes, 0, (n_blocks + 1) * 8, e->stream));
-  HIP_TRY(bc_render_sizes_launch(v, n_blocks, d_rows, d_bytes, e->stream));
+  HIP_TRY(text_sizes(v, n_blocks, d_rows, d_bytes, e->stream));
   std::vector<uint32_t> rows;
   std::vector<unsigned long long> prefix;
   try {
@@ -1984,7 +1974,7 @@ static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint
   auto emit = [&](uint64_t b0, uint64_t b1, uint64_t lo, uint64_t hi, uint64_t sub, uint64_t bytes) -> int {
     const int k = (int)(seg & 1);
     if (bytes) {
-      HIP_TRY(bc_render_write_launch(v, b0, b1 - b0, lo, hi, d_rows, d_bytes, sub, d_text[k], slot, e->stream));
+      HIP_TRY(text_write(v, b0, b1 - b0, lo, hi, d_rows, d_bytes, sub, d_text[k], slot, e->stream));
       HIP_TRY(hipMemcpyAsync(h_text[k], d_text[k], bytes, hipMemcpyDeviceToHost, e->stream));
     }
     pending[k] = bytes;
@@ -2005,7 +1995,7 @@ static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint
           b0 = b1;
           continue;
         }
-        r2 = emit(b0, b1, b0 * kRenderBlock, std::min<uint64_t>(v.T, b1 * kRenderBlock), prefix[b0], prefix[b1] - prefix[b0]);
+        r2 = emit(b0, b1, b0 * kRenderBlock, std::min<uint64_t>(n_keys, b1 * kRenderBlock), prefix[b0], prefix[b1] - prefix[b0]);
         if (r2 != BC_OK) return r2;
         b0 = b1;
         continue;
@@ -2016,8 +2006,8 @@ static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint
         HIP_TRY(g.hmalloc(&h_len, kRenderBlock * 4));
       }
       const uint64_t t0 = b0 * kRenderBlock;
-      const uint32_t n = (uint32_t)std::min<uint64_t>(kRenderBlock, v.T - t0);
-      HIP_TRY(bc_render_lens_launch(v, t0, n, d_len, e->stream));
+      const uint32_t n = (uint32_t)std::min<uint64_t>(kRenderBlock, n_keys - t0);
+      HIP_TRY(text_lens(v, t0, n, d_len, e->stream));
       HIP_TRY(hipMemcpyAsync(h_len, d_len, n * 4, hipMemcpyDeviceToHost, e->stream));
       HIP_TRY(hipStreamSynchronize(e->stream));
       uint32_t len[kRenderBlock];  // (a copy: h_len is reused by a later block while ranges are in flight)
@@ -2034,10 +2024,75 @@ static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint
     }
     return seg ? consume((int)((seg - 1) & 1)) : BC_OK;
   };
-  rc = run();
+  const int rc = run();
   (void)hipStreamSynchronize(e->stream);  // nothing of ours may still be writing the staging buffers when they go
   if (rc == BC_OK && n_rows) *n_rows = total_rows;
   return rc;
+}
+
+extern "C" {
+
+// The lines of the tuples for which some listed sample counts, in ascending tuple order (stream_text).
+static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, void* user,
+                       uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (P.sparse) {
+    set_error(std::string(who) + ": the plan keeps raw captures, whose rows are sequences, not indices: write them from "
+              "bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (!fn || (n_cols && !cols)) {
+    set_error(std::string(who) + ": null callback or sample list");
+    return BC_ERR_INVALID;
+  }
+  static_assert(bc::kRenderMaxG >= kMaxGroups, "a plan's counted barcodes fit the view");
+  bc::RenderView v;
+  memset(&v, 0, sizeof v);
+  v.G = e->barcode_num;
+  v.T = 1;
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    v.n[g] = P.groups[g0 + g].n_refs;
+    v.T *= v.n[g];
+  }
+  const uint64_t S = v.T ? e->table_entries / v.T : 0;
+  for (uint32_t c = 0; c < n_cols; ++c)
+    if (cols[c] >= S) {
+      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
+      return BC_ERR_INVALID;
+    }
+  int rc = dense_counts_ready(e);
+  if (rc) return rc;
+  if (n_cols == 0 || v.T == 0 || e->table_entries == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    if (bc_plan_n_counted(e->src_plan, g) != v.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
+      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+      return BC_ERR_STATE;
+    }
+    v.off_start[g] = e->label_off_start[g];
+    max_line += e->label_max[g];
+  }
+  if (max_line > bc::kRenderMaxLine) {
+    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
+              std::to_string(bc::kRenderMaxLine));
+    return BC_ERR_UNSUPPORTED;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
+  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
+  v.table = e->d_table;
+  v.bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
+  v.cols = d_cols;
+  v.n_cols = n_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
 }
 
 int bc_engine_render_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
@@ -2047,6 +2102,143 @@ int bc_engine_render_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, vo
 int bc_engine_render_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
                             uint64_t* n_rows) {
   return render_text(e, "bc_engine_render_merged", sample_idx, n_samples, fn, user, n_rows);
+}
+
+// ---- Single / Double enrichment as text (bc_enrich_render.h / bc_enrich_render.hip) ----
+
+// For every counted set, which entries share an ID: canon[off_g + i] = the smallest index of set g whose ID equals i's.
+// Built once per engine, next to the label pool; uploaded only when some set does share an ID.
+static int ensure_canon(bc_engine* e, const char* who) {
+  if (e->canon_ready) return BC_OK;
+  std::vector<uint32_t> canon;
+  bool shared = false;
+  try {
+    for (uint32_t g = 0; g < e->barcode_num; ++g) {
+      std::unordered_map<std::string, uint32_t> first;
+      const uint32_t n = bc_plan_n_counted(e->src_plan, g);
+      for (uint32_t i = 0; i < n; ++i) {
+        const char* id = bc_plan_counted_id(e->src_plan, g, i);
+        const uint32_t c = first.emplace(id ? id : "", i).first->second;
+        shared = shared || c != i;
+        canon.push_back(c);
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  if (shared) {
+    uint64_t d = 0;
+    const int rc = upload(e, canon.data(), canon.size() * 4, &d);
+    if (rc != BC_OK) return rc;
+    e->d_canon = (uint32_t*)(uintptr_t)d;
+  }
+  e->canon_ready = true;
+  return BC_OK;
+}
+
+// the view of one kind over the engine's sums (cols / n_cols left to the caller)
+static bc::EnrichRenderView enrich_view(const bc_engine* e, const EnrichShape& sh, uint64_t S, uint32_t kind) {
+  bc::EnrichRenderView v;
+  memset(&v, 0, sizeof v);
+  v.kind = kind;
+  v.G = sh.G;
+  v.K = kind == bc::kEnrichSingle ? sh.sum_n : sh.pairs;
+  v.sums = e->d_sums + (kind == bc::kEnrichSingle ? 0 : S * sh.sum_n);
+  v.canon = e->d_canon;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+  for (uint32_t g = 0; g < sh.G; ++g) {
+    v.n[g] = sh.n[g];
+    v.off_start[g] = e->label_off_start[g];
+  }
+  return v;
+}
+
+// The folded sums of the counts as they stand, on the device: computed by one pass over the table (bc_enrich_launch) and
+// the fold, then kept until the counts may have changed (counts_epoch).
+static int ensure_sums(bc_engine* e, const EnrichShape& sh, uint64_t S) {
+  const bool keep = e->own_table && !e->table_exposed;  // (nobody else can write the table between two renders)
+  if (e->d_sums && keep && e->sums_epoch == e->counts_epoch) return BC_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t n_single = S * sh.sum_n, n_double = S * sh.pairs;
+  e->sums_epoch = 0;
+  if (!e->d_sums) HIP_TRY(hipMalloc((void**)&e->d_sums, (size_t)(n_single + n_double) * 8));
+  HIP_TRY(hipMemsetAsync(e->d_sums, 0, (size_t)(n_single + n_double) * 8, e->stream));
+  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, e->d_sums,
+                           n_double ? e->d_sums + n_single : nullptr, e->stream));
+  if (e->d_canon) {
+    HIP_TRY(bc_enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichSingle), S, e->stream));
+    if (n_double) HIP_TRY(bc_enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichDouble), S, e->stream));
+  }
+  ++e->sums_passes;
+  if (keep) e->sums_epoch = e->counts_epoch;
+  return BC_OK;
+}
+
+static int render_enriched(bc_engine* e, const char* who, int kind, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
+                           void* user, uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  EnrichShape sh;
+  uint64_t S = 0;
+  if (!enrich_shape(e, who, &sh, &S)) return BC_ERR_UNSUPPORTED;
+  if (kind != BC_ENRICH_SINGLE && kind != BC_ENRICH_DOUBLE) {
+    set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
+    return BC_ERR_INVALID;
+  }
+  if (!fn || (n_cols && !cols)) {
+    set_error(std::string(who) + ": null callback or sample list");
+    return BC_ERR_INVALID;
+  }
+  for (uint32_t c = 0; c < n_cols; ++c)
+    if (cols[c] >= S) {
+      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
+      return BC_ERR_INVALID;
+    }
+  int rc = dense_counts_ready(e);
+  if (rc) return rc;
+  const uint64_t K = kind == BC_ENRICH_SINGLE ? sh.sum_n : sh.pairs;  // (no pairs below three counted barcodes)
+  if (n_cols == 0 || K == 0 || e->table_entries == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  if ((rc = ensure_canon(e, who)) != BC_OK) return rc;
+  uint32_t longest[2] = {0, 0};  // the two longest IDs of different sets
+  for (uint32_t g = 0; g < sh.G; ++g) {
+    if (bc_plan_n_counted(e->src_plan, g) != sh.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
+      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+      return BC_ERR_STATE;
+    }
+    const uint32_t m = e->label_max[g];
+    if (m > longest[0]) {
+      longest[1] = longest[0];
+      longest[0] = m;
+    } else if (m > longest[1]) {
+      longest[1] = m;
+    }
+  }
+  const uint64_t max_line = 1 + (sh.G - 1) + 21ull * n_cols + longest[0] + (kind == BC_ENRICH_DOUBLE ? longest[1] : 0u);
+  if (max_line > bc::kRenderMaxLine) {
+    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
+              std::to_string(bc::kRenderMaxLine));
+    return BC_ERR_UNSUPPORTED;
+  }
+  if ((rc = ensure_sums(e, sh, S)) != BC_OK) return rc;
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
+  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
+  bc::EnrichRenderView v = enrich_view(e, sh, S, (uint32_t)kind);
+  v.cols = d_cols;
+  v.n_cols = n_cols;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+int bc_engine_render_enriched(bc_engine* e, int kind, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_enriched(e, "bc_engine_render_enriched", kind, &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_enriched_merged(bc_engine* e, int kind, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn,
+                                     void* user, uint64_t* n_rows) {
+  return render_enriched(e, "bc_engine_render_enriched_merged", kind, sample_idx, n_samples, fn, user, n_rows);
 }
 
 // Random-barcode plans with a dense table: the count of a tuple is the number of distinct random barcodes seen with it
@@ -2059,6 +2251,7 @@ int bc_engine_materialize_table(bc_engine* e) {
     return BC_ERR_STATE;
   }
   HIP_TRY(hipSetDevice(e->device));
+  counts_changed(e);
   HIP_TRY(hipMemsetAsync(e->d_table, 0, e->table_entries * 4, e->stream));
   if (e->d_slots) {
     hipLaunchKernelGGL(set_to_table_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->n_slots,
@@ -2143,6 +2336,7 @@ int bc_engine_import_keys(bc_engine* e, const void* d_keys, uint64_t n, uint64_t
   if (n == 0) return BC_OK;
   HIP_TRY(hipSetDevice(e->device));
   e->table_materialized = false;
+  counts_changed(e);
   int rc = set_reserve(e, n);
   if (rc) return rc;
   ScratchGuard g;
@@ -2212,6 +2406,7 @@ int bc_engine_import_counts(bc_engine* e, const void* d_keys, const void* d_coun
     return BC_ERR_INVALID;
   }
   HIP_TRY(hipSetDevice(e->device));
+  counts_changed(e);
   if ((rc = set_reserve(e, n))) return rc;
   if (e->key_words > 1)
     hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, (const unsigned long long*)d_keys,
@@ -2227,6 +2422,7 @@ int bc_engine_import_counts(bc_engine* e, const void* d_keys, const void* d_coun
 
 int bc_engine_clear_keys(bc_engine* e) {
   HIP_TRY(hipSetDevice(e->device));
+  counts_changed(e);
   if (e->d_slots) {
     hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(e->n_slots * e->key_words)), dim3(256), 0, e->stream, e->d_slots,
                        e->n_slots * e->key_words);
@@ -2390,6 +2586,10 @@ int bc_engine_count_log_folds(const bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
+int bc_engine_enrich_render_passes(const bc_engine* e, uint64_t* n) {
+  *n = e->sums_passes;
+  return BC_OK;
+}
 int bc_engine_gz_blocks_inflated(const bc_engine* e, uint64_t* n) {
   *n = e->gz_blocks;
   return BC_OK;

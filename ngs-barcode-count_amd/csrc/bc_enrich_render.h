@@ -1,0 +1,201 @@
+// bc_enrich_render.h -- the text of a dense plan's Single and Double enrichment files (bc_engine_render_enriched /
+// bc_engine_render_enriched_merged): the lane-level pieces, shared by the kernels of bc_enrich_render.hip and the host
+// harness tests/render/enrich_render_host.cpp (which runs this SAME code under AddressSanitizer; never a product path on
+// the host).
+//
+// A line belongs to one key k of one sample's slice of the marginal sums (bc_engine_enrich's layout; G counted barcodes,
+// N_g = size of known set g, SUM = sum N_g, P = sum over pairs g < h of N_g * N_h, pairs in add_double's order):
+//     Single  k in [0, SUM)  ->  (g, i)        k = off_g + i
+//     Double  k in [0, P)    ->  (g, h, i, j)  k = poff_(g,h) + i * N_h + j
+// and to an ordered list of sample columns.  It has G fields joined by commas -- field g holds id_g (and field h id_h),
+// every other field is empty, as add_single / add_double build the key (info.rs:840-904) -- then one count per column:
+//     ,id,,c_0,c_1,..\n        c_m = sums[cols[m] * K + k], a u64 in decimal
+// and exists when some c_m is not zero.  IDs are copied verbatim from the label pool (bc_render.h).
+//
+// Entries of one known set whose IDs are byte-equal are ONE key of the reference's maps (they are keyed by text): the
+// sums are folded before any line is written -- enrich_fold_target names, for every key, the key of the smallest indices
+// carrying the same IDs; a key that is not its own target adds its sum there and becomes zero, so it has no line.
+// Text that coincides ACROSS groups or pairs (possible only when some ID is empty: ",," is the empty ID of every group)
+// is NOT merged: such plans are not for this renderer.
+//
+// Nothing here indexes a local array: a line is measured and written from its END backwards, digit by digit.
+#ifndef BC_ENRICH_RENDER_H
+#define BC_ENRICH_RENDER_H
+
+#include "bc_render.h"
+
+namespace bc {
+
+constexpr uint32_t kEnrichSingle = 1, kEnrichDouble = 2;  // BC_ENRICH_SINGLE / BC_ENRICH_DOUBLE
+
+struct EnrichRenderView {
+  const unsigned long long* sums;  // this kind's sums, folded: entry s * K + k
+  const uint32_t* cols;            // sample index of every column
+  const uint32_t* canon;           // canon[off_g + i]: the smallest index of set g with i's ID; NULL: no set shares an ID
+  const uint32_t* label_off;       // the label pool (bc_render.h)
+  const uint8_t* label_bytes;
+  uint64_t K;                      // keys per sample: SUM or P
+  uint32_t n_cols;
+  uint32_t G;
+  uint32_t kind;                   // kEnrichSingle | kEnrichDouble
+  uint32_t n[kRenderMaxG];          // N_g
+  uint32_t off_start[kRenderMaxG];  // where group g's N_g + 1 offsets start in label_off
+};
+
+struct EnrichKey {
+  uint32_t g, h;  // the fields that hold an ID (h = g for a single)
+  uint32_t i, j;  // indices into sets g and h
+};
+
+// x / 10 by multiplication: the high half of x * ceil(2^67 / 10), shifted by 3 -- exact for every u64
+BC_HD uint64_t enrich_div10(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(x, 0xCCCCCCCCCCCCCCCDull) >> 3;
+#else
+  return (uint64_t)(((unsigned __int128)x * 0xCCCCCCCCCCCCCCCDull) >> 64) >> 3;
+#endif
+}
+
+// decimal digits of x: 1 .. 20
+BC_HD uint32_t enrich_digits(uint64_t x) {
+  if ((x >> 32) == 0) return render_digits((uint32_t)x);
+  uint32_t d = 10;
+  uint64_t p = 10000000000ull;  // 10^d
+  while (d < 19 && x >= p) {
+    p *= 10u;
+    ++d;
+  }
+  return d + (x >= p);  // (at d = 19 p = 10^19 still fits; 10^20 does not)
+}
+
+// key -> the fields and indices it stands for (k < v.K)
+BC_HD EnrichKey enrich_key(const EnrichRenderView& v, uint64_t k) {
+  EnrichKey key = {0u, 0u, 0u, 0u};
+  if (v.kind == kEnrichSingle) {
+    uint32_t g = 0;
+    while (g + 1 < v.G && k >= v.n[g]) k -= v.n[g++];
+    key.g = key.h = g;
+    key.i = key.j = (uint32_t)k;
+    return key;
+  }
+  for (uint32_t g = 0; g + 1 < v.G; ++g)
+    for (uint32_t h = g + 1; h < v.G; ++h) {
+      const uint64_t sz = (uint64_t)v.n[g] * v.n[h];
+      if (k < sz || (g + 2 == v.G)) {  // (the last pair takes what is left)
+        key.g = g;
+        key.h = h;
+        key.j = render_take_digit(k, v.n[h]);
+        key.i = (uint32_t)k;
+        return key;
+      }
+      k -= sz;
+    }
+  return key;
+}
+
+// off_g = N_0 + .. + N_{g-1}: where set g starts in v.canon (and in a single's key space)
+BC_HD uint64_t enrich_set_off(const EnrichRenderView& v, uint32_t g) {
+  uint64_t off = 0;
+  for (uint32_t x = 0; x < g; ++x) off += v.n[x];
+  return off;
+}
+
+// the key that k's sum belongs to: the same fields with the smallest indices that carry the same IDs (k itself when it
+// is canonical, and always without v.canon)
+BC_HD uint64_t enrich_fold_target(const EnrichRenderView& v, uint64_t k) {
+  if (!v.canon) return k;
+  const EnrichKey key = enrich_key(v, k);
+  const uint32_t ci = v.canon[enrich_set_off(v, key.g) + key.i];
+  if (v.kind == kEnrichSingle) return k - key.i + ci;
+  const uint32_t cj = v.canon[enrich_set_off(v, key.h) + key.j];
+  const uint64_t nh = v.n[key.h];
+  return k - ((uint64_t)key.i * nh + key.j) + ((uint64_t)ci * nh + cj);
+}
+
+BC_HD uint64_t enrich_sum(const EnrichRenderView& v, uint32_t c, uint64_t k) { return v.sums[(uint64_t)v.cols[c] * v.K + k]; }
+
+BC_HD uint32_t enrich_label_len(const EnrichRenderView& v, uint32_t g, uint32_t i) {
+  const uint32_t* o = v.label_off + v.off_start[g] + i;
+  return o[1] - o[0];
+}
+
+// bytes of key k's line, '\n' included; 0 when every column is zero (no line)
+BC_HD uint32_t enrich_row_len(const EnrichRenderView& v, uint64_t k) {
+  uint64_t any = 0;
+  uint32_t len = 1u + (v.G ? v.G - 1u : 0u);  // '\n' and the commas between the fields
+  for (uint32_t c = 0; c < v.n_cols; ++c) {
+    const uint64_t x = enrich_sum(v, c, k);
+    any |= x;
+    len += 1u + enrich_digits(x);  // ",count"
+  }
+  if (!any) return 0;
+  const EnrichKey key = enrich_key(v, k);
+  len += enrich_label_len(v, key.g, key.i);
+  if (v.kind == kEnrichDouble) len += enrich_label_len(v, key.h, key.j);
+  return len;
+}
+
+// Writes the part of key k's line (len = enrich_row_len, not 0) that falls into the window dst[0 .. win): the line starts
+// at window position `at`, which may be negative or beyond the window (as render_row_write).
+template <typename Byte>
+BC_HD void enrich_row_write(const EnrichRenderView& v, uint64_t k, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
+  int64_t p = at + (int64_t)len;  // one past the byte written next (the line is written backwards)
+#define BC_ENRICH_PUT(ch)                                 \
+  do {                                                    \
+    --p;                                                  \
+    if (p >= 0 && p < (int64_t)win) dst[p] = (Byte)(ch);  \
+  } while (0)
+  BC_ENRICH_PUT('\n');
+  for (uint32_t c = v.n_cols; c-- > 0;) {
+    uint64_t x = enrich_sum(v, c, k);
+    do {
+      const uint64_t q = enrich_div10(x);
+      BC_ENRICH_PUT('0' + (uint32_t)(x - q * 10u));
+      x = q;
+    } while (x);
+    BC_ENRICH_PUT(',');
+  }
+  const EnrichKey key = enrich_key(v, k);
+  for (uint32_t f = v.G; f-- > 0;) {
+    // (for a single h == g: the first test takes it)
+    if (f == key.h || f == key.g) {
+      const uint32_t* o = v.label_off + v.off_start[f] + (f == key.h ? key.j : key.i);
+      const uint32_t a = o[0], n = o[1] - o[0];
+      // the label lies at [p - n, p): only its bytes inside the window are touched
+      int64_t lo = p - (int64_t)n, hi = p;
+      p = lo;
+      if (lo < 0) lo = 0;
+      if (hi > (int64_t)win) hi = (int64_t)win;
+      for (int64_t w = lo; w < hi; ++w) dst[w] = (Byte)v.label_bytes[a + (uint32_t)(w - p)];
+    }
+    if (f) BC_ENRICH_PUT(',');
+  }
+#undef BC_ENRICH_PUT
+}
+
+// the names bc_text_kernels.h reaches a view's lane code by
+BC_HD uint64_t text_keys(const EnrichRenderView& v) { return v.K; }
+BC_HD uint32_t text_line_len(const EnrichRenderView& v, uint64_t k) { return enrich_row_len(v, k); }
+template <typename Byte>
+BC_HD void text_line_write(const EnrichRenderView& v, uint64_t k, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
+  enrich_row_write(v, k, len, dst, at, win);
+}
+
+}  // namespace bc
+
+#if defined(__HIPCC__)
+// The kernels (bc_enrich_render.hip); all enqueue on `stream`.  A block is kRenderBlock consecutive keys; the three
+// passes are those of bc_render.h.
+hipError_t bc_enrich_render_sizes_launch(const bc::EnrichRenderView& v, uint64_t n_blocks, uint32_t* d_rows,
+                                         unsigned long long* d_bytes, hipStream_t stream);
+hipError_t bc_enrich_render_lens_launch(const bc::EnrichRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len,
+                                        hipStream_t stream);
+hipError_t bc_enrich_render_write_launch(const bc::EnrichRenderView& v, uint64_t b0, uint64_t n_blocks, uint64_t lo, uint64_t hi,
+                                         const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
+                                         uint64_t out_cap, hipStream_t stream);
+// Folds the sums of one kind for n_samples samples (v.sums writable, v.canon not NULL): every key that is not its own
+// enrich_fold_target adds its sum to the target and becomes zero.
+hipError_t bc_enrich_fold_launch(const bc::EnrichRenderView& v, uint64_t n_samples, hipStream_t stream);
+#endif
+
+#endif

@@ -114,6 +114,14 @@ BC_HD void render_row_write(const RenderView& v, uint64_t t, uint32_t len, Byte*
 #undef BC_RENDER_PUT
 }
 
+// the names bc_text_kernels.h reaches a view's lane code by
+BC_HD uint64_t text_keys(const RenderView& v) { return v.T; }
+BC_HD uint32_t text_line_len(const RenderView& v, uint64_t t) { return render_row_len(v, t); }
+template <typename Byte>
+BC_HD void text_line_write(const RenderView& v, uint64_t t, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
+  render_row_write(v, t, len, dst, at, win);
+}
+
 }  // namespace bc
 
 #if defined(__HIPCC__)

@@ -1,0 +1,101 @@
+"""Builds and runs tests/render/enrich_render_host: the enrichment renderer's lane code (csrc/bc_enrich_render.h) on the
+host, compiled with AddressSanitizer and UndefinedBehaviorSanitizer, as a child process; and the Python rendering every
+enrichment render test compares with.  TEST-ONLY."""
+import os
+import struct
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ngs-barcode-count_amd", "csrc")
+EXE = os.path.join(ROOT, "tests", "render", "enrich_render_host")
+SRC = os.path.join(ROOT, "tests", "render", "enrich_render_host.cpp")
+DEPS = [SRC] + [os.path.join(CSRC, h) for h in ("bc_enrich_render.h", "bc_render.h", "bc_intrin.h")]
+SINGLE, DOUBLE = 1, 2
+
+
+def exe():
+    if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in DEPS):
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
+                               "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-o", EXE, SRC])
+    return EXE
+
+
+def keys(ids, kind):
+    """the key space of one sample in ascending key index: [(fields, text)], fields = ((g, i),) or ((g, i), (h, j)), text
+    = the G comma-joined fields of the line.  Doubles exist only from three counted barcodes on."""
+    G = len(ids)
+
+    def text(fields):
+        cells = [b""] * G
+        for g, i in fields:
+            cells[g] = ids[g][i]
+        return b",".join(cells)
+
+    if kind == SINGLE:
+        out = [((g, i),) for g in range(G) for i in range(len(ids[g]))]
+    elif G < 3:
+        out = []
+    else:
+        out = [((g, i), (h, j)) for g in range(G) for h in range(g + 1, G) for i in range(len(ids[g]))
+               for j in range(len(ids[h]))]
+    return [(f, text(f)) for f in out]
+
+
+def render_py(ids, sums, kind, cols):
+    """ids: per counted barcode the list of IDs (bytes); sums[s][k]: the RAW sum of sample s, key k; cols: sample indices
+    -> (text, lines).  Keys of the same fields whose IDs are byte-equal are one key, at the place of the first of them
+    (keyed by the ID bytes, as the reference's maps are by text); the same text in different fields stays apart.  The
+    definition the device code is held to."""
+    ks = keys(ids, kind)
+    first, total = {}, {}
+    for k, (fields, text) in enumerate(ks):
+        name = tuple((g, ids[g][i]) for g, i in fields)
+        at = first.setdefault(name, k)
+        for s in range(len(sums)):
+            total[(s, at)] = total.get((s, at), 0) + int(sums[s][k])
+    out, lines = [], 0
+    for k, (fields, text) in enumerate(ks):
+        if first[tuple((g, ids[g][i]) for g, i in fields)] != k:
+            continue
+        cs = [total[(s, k)] for s in cols]
+        if not any(cs):
+            continue
+        out.append(b",".join([text] + [str(c).encode() for c in cs]) + b"\n")
+        lines += 1
+    return b"".join(out), lines
+
+
+def canon_of(ids):
+    """per set, back to back: the smallest index carrying each entry's ID; None when no set shares one"""
+    canon, shared = [], False
+    for g in ids:
+        first = {}
+        own = [first.setdefault(i, k) for k, i in enumerate(g)]
+        shared = shared or own != list(range(len(g)))
+        canon += own
+    return canon if shared else None
+
+
+def run(ids, sums, kind, cols, tmp_path, tag="case", win=4096, pad=0, canon="auto"):
+    """sums[s][k]: raw sums -> (text, lines) from the harness"""
+    if canon == "auto":
+        canon = canon_of(ids)
+    fin, fout = os.path.join(str(tmp_path), tag + ".in"), os.path.join(str(tmp_path), tag + ".out")
+    flat = [int(x) for row in sums for x in row]
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<8I", len(ids), kind, len(cols), len(sums), win, pad, 1 if canon is not None else 0, 0))
+        f.write(struct.pack("<%dI" % len(ids), *[len(g) for g in ids]))
+        f.write(struct.pack("<%dI" % len(cols), *cols))
+        for g in ids:
+            for i in g:
+                f.write(struct.pack("<I", len(i)) + i)
+        if canon is not None:
+            f.write(struct.pack("<%dI" % len(canon), *canon))
+        f.write(struct.pack("<%dQ" % len(flat), *flat))
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([exe(), fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0 and not p.stderr, "%s: exit %d\n%s" % (tag, p.returncode, p.stderr.decode(errors="replace")[-4000:])
+    raw = open(fout, "rb").read()
+    lines, nbytes = struct.unpack_from("<2Q", raw, 0)
+    assert len(raw) == 16 + nbytes
+    return raw[16:], lines
