@@ -745,6 +745,7 @@ int bc_engine_reduce_all(bc_engine* e, bc_comm* c, int root, uint64_t counters[B
   if (!sparse) {
     // (two-level counting: the bit map travels inside the packed bytes -- table + bit --, not through a fold pass)
     uint32_t* table = (uint32_t*)bc_internal_table_unfolded(e, &ops.engine_bits);
+    if (!table) return BC_ERR_HIP;  // (a pending reset could not be run: the error is set)
     ops.engine_table = table;
     int form = 0;
     if ((rc = status(reduce_tables(t, ops, table, (const uint32_t*)ops.engine_bits, bc_engine_table_entries(e), root, &form))))

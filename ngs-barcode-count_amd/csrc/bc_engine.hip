@@ -604,6 +604,19 @@ struct bc_engine {
   uint64_t gz_blocks = 0;            // BGZF blocks inflated on the device for this engine (bc_engine_gz_blocks_inflated)
   uint64_t log_folds = 0;            // folds run since the engine was created (bc_engine_count_log_folds)
   uint32_t* d_fold_meta = nullptr;   // [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each
+  // What the last reset owes (settle_owed()): a reset only records it, and whoever touches table, dirty map or bit map
+  // next pays it first, on the engine's stream -- except a log-mode submit, whose match kernel touches none of them:
+  // there the table's part runs on reset_stream beside the match kernel and is joined before the fold
+  // (BC_COUNT_LOG_DEFER_RESET=0|1), and the fold takes the bit map as all zero without anyone writing the zeros first
+  // (bc_fold.h, a fresh fold; BC_COUNT_LOG_FRESH=0|1).  The table's part is only ever owed for a table nobody else can
+  // see (engine-owned, its pointer not handed out): whoever holds a pointer may order work after the reset by the stream.
+  bool owed_table = false;           // the dirty-block reset, or (owed_table_all) table and dirty map zeroed whole
+  bool owed_table_all = false;
+  bool owed_bits = false;            // the bit map zeroed
+  bool defer_reset = true;
+  bool fold_fresh = true;
+  hipStream_t reset_stream = nullptr;  // created with the first deferred reset
+  hipEvent_t reset_fork = nullptr, reset_join = nullptr;
   unsigned long long* d_counters = nullptr;
   uint32_t barcode_num = 0;
   uint32_t n_sets[kMaxGroups] = {0};
@@ -702,6 +715,10 @@ static void engine_free(bc_engine* e) {
   if (e->d_sums) (void)hipFree(e->d_sums);
   if (e->d_counters) (void)hipFree(e->d_counters);
   if (e->d_plan) (void)hipFree(e->d_plan);
+  if (e->reset_stream) (void)hipStreamSynchronize(e->reset_stream);
+  if (e->reset_fork) (void)hipEventDestroy(e->reset_fork);
+  if (e->reset_join) (void)hipEventDestroy(e->reset_join);
+  if (e->reset_stream) (void)hipStreamDestroy(e->reset_stream);
   if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -824,6 +841,8 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
   }
   if (const char* cl = getenv("BC_COUNT_LOG")) e->count_log = strcmp(cl, "auto") == 0 ? 2 : atoi(cl);
   if (const char* ch = getenv("BC_COUNT_LOG_HOT")) e->log_hot = atoi(ch) != 0;
+  if (const char* cd = getenv("BC_COUNT_LOG_DEFER_RESET")) e->defer_reset = atoi(cd) != 0;
+  if (const char* cf = getenv("BC_COUNT_LOG_FRESH")) e->fold_fresh = atoi(cf) != 0;
   if (const char* cm = getenv("BC_COUNT_LOG_MIN_READS")) e->log_min_reads = strtoull(cm, nullptr, 0);
   if (const char* cc = getenv("BC_COUNT_LOG_CHUNK")) {
     const uint64_t c = strtoull(cc, nullptr, 0) & ~63ull;
@@ -902,8 +921,9 @@ static bool log_mode_for(const bc_engine* e, uint64_t n_reads) {
 // the log and its grouped copy: allocated once per engine, grown to the largest chunk seen (at most log_chunk)
 static int ensure_log(bc_engine* e, uint64_t entries) {
   if (!e->d_fold_meta) {
-    HIP_TRY(hipMalloc((void**)&e->d_fold_meta, 4 * (kFoldMaxBuckets + 1) * 4));
-    HIP_TRY(hipMemsetAsync(e->d_fold_meta, 0, 4 * (kFoldMaxBuckets + 1) * 4, e->stream));
+    // (a fifth section: the saved bucket counts of the BC_FOLD_REUSE_CNT experiment)
+    HIP_TRY(hipMalloc((void**)&e->d_fold_meta, 5 * (kFoldMaxBuckets + 1) * 4));
+    HIP_TRY(hipMemsetAsync(e->d_fold_meta, 0, 5 * (kFoldMaxBuckets + 1) * 4, e->stream));
   }
   if (entries <= e->log_cap) return BC_OK;
   entries = (entries + 63) & ~63ull;
@@ -920,14 +940,118 @@ static int ensure_log(bc_engine* e, uint64_t entries) {
   return BC_OK;
 }
 
-// the fold of the log's first n entries into bit map + table (bc_fold.h), on the engine's stream
-static int fold_log(bc_engine* e, uint64_t n) {
+// the fold of the log's first n entries into bit map + table (bc_fold.h), on the engine's stream; fresh: onto a bit map
+// that is owed its zeroing (the fold writes every word of it instead)
+static int fold_log(bc_engine* e, uint64_t n, bool fresh) {
   const uint32_t nb = (uint32_t)((e->table_entries + (1ull << kFoldBucketShift) - 1) >> kFoldBucketShift);
   uint8_t* dirty = e->h.plan.dirty_off ? reinterpret_cast<uint8_t*>(e->d_bits + e->h.plan.dirty_off) : nullptr;
+  bool have_cnt = false;
+#ifdef BC_EXPERIMENT
+  // BC_FOLD_REUSE_CNT=1 (perf experiment, for a benchmark that submits the SAME reads every time): the bucket counts
+  // of the engine's first fold are kept and copied back (4 KB) instead of running bc_fold_hist again -- what a step
+  // costs when the counts come for free, i.e. the most that counting them inside the match kernel could save
+  static const bool reuse_cnt = getenv("BC_FOLD_REUSE_CNT") && atoi(getenv("BC_FOLD_REUSE_CNT")) != 0;
+  uint32_t* saved = e->d_fold_meta + 4 * (kFoldMaxBuckets + 1);
+  if (reuse_cnt && e->log_folds > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_fold_meta, saved, (kFoldMaxBuckets + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
+    have_cnt = true;
+  }
+#endif
   HIP_TRY(fold_launch(e->stream, (const uint32_t*)e->d_log, n, e->d_grouped, e->d_fold_meta, nb, e->d_bits, e->n_bit_words,
-                      e->d_table, dirty, e->n_cus));
+                      e->d_table, dirty, e->n_cus, 0, 0, fresh, have_cnt));
+#ifdef BC_EXPERIMENT
+  if (reuse_cnt && e->log_folds == 0) {
+    // (scan has zeroed cnt by now: count once more, for the copy)
+    const uint64_t n4 = n / 4 + 1;
+    hipLaunchKernelGGL(bc_fold_hist, dim3((uint32_t)std::min<uint64_t>((n4 + kFoldTPB - 1) / kFoldTPB, 4ull * e->n_cus)), dim3(kFoldTPB), 0,
+                       e->stream, (const uint32_t*)e->d_log, n, nb, e->d_fold_meta);
+    HIP_TRY(hipMemcpyAsync(saved, e->d_fold_meta, (kFoldMaxBuckets + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_fold_meta, 0, (kFoldMaxBuckets + 1) * 4, e->stream));
+  }
+#endif
   ++e->log_folds;
   return BC_OK;
+}
+
+static uint32_t grid_for(uint64_t n);
+
+// The two parts of an owed reset (bc_engine::owed_*), enqueued on `st`; each clears its flag once it is enqueued.
+static int settle_table_on(bc_engine* e, hipStream_t st) {
+  if (!e->owed_table) return BC_OK;
+  const uint64_t dirty_off = e->h.plan.dirty_off;
+  if (!e->owed_table_all) {
+    // two-level counting: after a short job the table is almost all zeros -- first occurrences live in the bit map --
+    // and every add to it flagged its 256-byte block: zero those blocks and the flags (16.5 GB of memset -> 0.06 GB)
+    hipLaunchKernelGGL(sparse_reset_kernel, dim3(grid_for(e->dirty_bytes / 16)), dim3(256), 0, st, e->d_table,
+                       reinterpret_cast<uint4*>(e->d_bits + dirty_off), e->dirty_bytes / 16, e->table_entries);
+    HIP_TRY(hipGetLastError());
+  } else {
+    if (e->d_table) HIP_TRY(hipMemsetAsync(e->d_table, 0, e->table_entries * 4, st));
+    if (e->d_bits && dirty_off) HIP_TRY(hipMemsetAsync(e->d_bits + dirty_off, 0, e->dirty_bytes, st));
+  }
+  e->owed_table = e->owed_table_all = false;
+  return BC_OK;
+}
+static int settle_bits_on(bc_engine* e, hipStream_t st) {
+  if (!e->owed_bits) return BC_OK;
+  HIP_TRY(hipMemsetAsync(e->d_bits, 0, e->n_bit_words * 4, st));
+  e->owed_bits = false;
+  return BC_OK;
+}
+// Everything owed, on the engine's stream: first thing in every path that reads or writes table, dirty map or bit map.
+static int settle_owed(bc_engine* e) {
+  int rc = settle_table_on(e, e->stream);
+  if (rc == BC_OK) rc = settle_bits_on(e, e->stream);
+  return rc;
+}
+
+// Who pays what a reset owes when a match launch meets it -- the one place that decides it.
+//   kOwedMain   on the engine's stream, ahead of the match kernel (what every other path does: settle_owed)
+//   kOwedSide   on reset_stream beside the match kernel, joined before the fold (BC_COUNT_LOG_DEFER_RESET)
+//   kOwedFresh  never: the first fold takes the bit map as all zero and writes every word of it (BC_COUNT_LOG_FRESH)
+// table_untouched: a log-mode launch whose kernel writes neither table nor dirty map.  No log-mode kernel touches the
+// bit map, so its part can go aside or stay owed in any log-mode launch.
+enum OwedWhere { kOwedMain, kOwedSide, kOwedFresh };
+struct OwedPlan {
+  OwedWhere table, bits;
+};
+static OwedPlan owed_plan(const bc_engine* e, bool use_log, bool table_untouched) {
+  OwedPlan p;
+  p.table = table_untouched && e->defer_reset ? kOwedSide : kOwedMain;
+  p.bits = !use_log ? kOwedMain : (e->fold_fresh ? kOwedFresh : (e->defer_reset ? kOwedSide : kOwedMain));
+  return p;
+}
+
+// A log-mode submit with something owed: the parts that owed_plan() sends aside on reset_stream, after everything
+// queued on the engine's stream so far.  *join: the engine's stream has to wait for reset_join before the fold.
+// Whatever cannot be forked is settled on the engine's stream instead.
+static int fork_owed(bc_engine* e, const OwedPlan& plan, bool* join) {
+  *join = false;
+  const bool bits_stay_owed = plan.bits != kOwedSide;
+  if (plan.table != kOwedSide && e->owed_table) return settle_owed(e);  // (not reached: launch_match settled it)
+  if (!e->owed_table && (bits_stay_owed || !e->owed_bits)) return BC_OK;
+  if (!e->reset_stream) {
+    if (hipStreamCreateWithFlags(&e->reset_stream, hipStreamNonBlocking) != hipSuccess) e->reset_stream = nullptr;
+    if (e->reset_stream && (hipEventCreateWithFlags(&e->reset_fork, hipEventDisableTiming) != hipSuccess ||
+                            hipEventCreateWithFlags(&e->reset_join, hipEventDisableTiming) != hipSuccess)) {
+      (void)hipStreamDestroy(e->reset_stream);
+      e->reset_stream = nullptr;
+    }
+  }
+  if (!e->reset_stream || hipEventRecord(e->reset_fork, e->stream) != hipSuccess ||
+      hipStreamWaitEvent(e->reset_stream, e->reset_fork, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    return settle_owed(e);
+  }
+  int rc = settle_table_on(e, e->reset_stream);
+  if (rc == BC_OK && !bits_stay_owed) rc = settle_bits_on(e, e->reset_stream);
+  // (joined whatever happened: what did get onto reset_stream must not run on beside a later writer)
+  if (hipEventRecord(e->reset_join, e->reset_stream) != hipSuccess) {
+    HIP_TRY(hipStreamSynchronize(e->reset_stream));
+    return rc;
+  }
+  *join = true;
+  return rc;
 }
 
 // s: match_shape() of the batch; NW = s.generic_nw
@@ -938,6 +1062,19 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   // folded before the next one overwrites it.  (The hot-counter cache keeps its LDS either way: the same code object.)
   const bool use_log = log_mode_for(e, n_reads);
   const bool hot_on = !use_log || e->log_hot;
+  // In log mode the kernel reads and writes only the reads, the log and the outcome counters -- unless the hot-counter
+  // cache flushes to the table or the plan's search queue adds to it directly (neither touches the bit map): what a
+  // reset owes can then wait for the fold (owed_plan).  Everyone else settles first.
+  const bool table_untouched = use_log && !hot_on && !e->h.plan.defer_search();
+  const OwedPlan owed = owed_plan(e, use_log, table_untouched);
+  if (owed.table == kOwedMain) {
+    const int rc = settle_table_on(e, e->stream);
+    if (rc != BC_OK) return rc;
+  }
+  if (owed.bits == kOwedMain) {
+    const int rc = settle_bits_on(e, e->stream);
+    if (rc != BC_OK) return rc;
+  }
   const uint32_t flags = (e->pipe ? 1u : 0u) | (s.tables_generic ? 2u : 0u) | (s.hot_generic && hot_on ? 4u : 0u);
   if (s.lds + 64 > e->lds_limit) {
     set_error("read stride too large for one LDS tile");
@@ -970,6 +1107,23 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     if (rc != BC_OK) return rc;
   }
   const uint64_t chunk = use_log ? e->log_chunk : n_reads;
+  bool join = false;
+  if (use_log) {
+    const int rc = fork_owed(e, owed, &join);
+    if (rc != BC_OK) {
+      if (join) (void)hipStreamWaitEvent(e->stream, e->reset_join, 0);
+      (void)settle_owed(e);
+      return rc;
+    }
+  }
+  // (an error below leaves through here: the side stream joined, and what is still owed stays owed for the next comer)
+  struct JoinGuard {
+    bc_engine* e;
+    bool* join;
+    ~JoinGuard() {
+      if (*join) (void)hipStreamWaitEvent(e->stream, e->reset_join, 0);
+    }
+  } join_guard{e, &join};
   for (uint64_t c0 = 0; c0 < n_reads; c0 += chunk) {
     const uint64_t n_c = std::min<uint64_t>(chunk, n_reads - c0);
     const uint8_t* a_seq = (const uint8_t*)d_seq + c0 * stride;
@@ -996,8 +1150,14 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     }
     HIP_TRY(hipGetLastError());
     if (use_log) {
-      const int rc = fold_log(e, n_c);
-      if (rc != BC_OK) return rc;
+      if (join) {
+        HIP_TRY(hipStreamWaitEvent(e->stream, e->reset_join, 0));
+        join = false;
+      }
+      const bool fresh = e->owed_bits;  // (kOwedFresh, and only the first chunk after a reset)
+      const int rc = fold_log(e, n_c, fresh);
+      if (rc != BC_OK) return rc;  // (a fresh fold that failed: the map stays owed its zeros)
+      e->owed_bits = false;
     }
   }
   if (e->d_bits) {
@@ -1036,8 +1196,9 @@ static int ensure_long(bc_engine* e) {
 
 static int launch_long(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens,
                        uint32_t stride, uint32_t read_len, uint64_t n_reads, uint64_t trace_off) {
-  const int rc = ensure_long(e);
+  int rc = ensure_long(e);
   if (rc != BC_OK) return rc;
+  if ((rc = settle_owed(e)) != BC_OK) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (e->timing) {
     HIP_TRY(hipEventCreate(&e0));
@@ -1288,6 +1449,8 @@ int bc_engine_submit_host(bc_engine* e, const void* seq, const void* qual, const
 
 // two-level counting: the bits into the table, the map cleared (enqueued on the engine's stream)
 static int fold_bits(bc_engine* e) {
+  const int owed_rc = settle_owed(e);
+  if (owed_rc != BC_OK) return owed_rc;
   if (!e->bits_dirty) return BC_OK;
   // few bits (under one in sixteen entries): one lane per word of the map, a table access per set bit; many: a
   // streaming pass over the table
@@ -1306,6 +1469,10 @@ static int fold_bits(bc_engine* e) {
 
 int bc_engine_sync(bc_engine* e) {
   HIP_TRY(hipSetDevice(e->device));
+  {
+    const int rc = settle_owed(e);  // (reset(); sync() costs and means what it always did)
+    if (rc != BC_OK) return rc;
+  }
   // Two-level counting: a table somebody else can see -- caller-owned memory, or an engine-owned table whose pointer
   // has been handed out (bc_engine_table_ptr) -- holds the whole counts from here on; an engine-owned one nobody has
   // asked for keeps its bits apart: bc_engine_finish reads bits and table as they stand.
@@ -1325,19 +1492,23 @@ int bc_engine_reset_results(bc_engine* e) { return reset_impl(e, false); }
 static int reset_impl(bc_engine* e, bool counters_too) {
   HIP_TRY(hipSetDevice(e->device));
   counts_changed(e);
+  // what an earlier reset still owes goes first: its dirty-block pass is what makes the flags mean what they say
+  {
+    const int rc = settle_owed(e);
+    if (rc != BC_OK) return rc;
+  }
+  // Nothing is zeroed here: the reset is recorded as owed (bc_engine::owed_*) and paid by whoever needs it.  With a
+  // dirty-block map whose flags can be trusted the table's part is the dirty-block pass (sparse_reset_kernel), otherwise
+  // table and flags are zeroed whole; the bit map is zeroed either way.
   const uint64_t dirty_off = e->h.plan.dirty_off;
-  if (e->d_bits && dirty_off && !e->table_all_dirty) {
-    // two-level counting: after a short job the table is almost all zeros -- first occurrences live in the bit map --
-    // and every add to it flagged its 256-byte block: zero those blocks and the bit map (16.5 GB of memset -> 0.5 GB)
-    hipLaunchKernelGGL(sparse_reset_kernel, dim3(grid_for(e->dirty_bytes / 16)), dim3(256), 0, e->stream, e->d_table,
-                       reinterpret_cast<uint4*>(e->d_bits + dirty_off), e->dirty_bytes / 16, e->table_entries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(e->d_bits, 0, e->n_bit_words * 4, e->stream));
-  } else {
-    if (e->d_table) HIP_TRY(hipMemsetAsync(e->d_table, 0, e->table_entries * 4, e->stream));
-    if (e->d_bits)
-      HIP_TRY(hipMemsetAsync(e->d_bits, 0, dirty_off ? (size_t)(dirty_off * 4 + e->dirty_bytes) : (size_t)(e->n_bit_words * 4), e->stream));
-    e->table_all_dirty = !e->own_table || e->table_exposed;  // (whoever holds the pointer may write it again)
+  e->owed_table = e->d_table != nullptr;
+  e->owed_table_all = !(e->d_bits && dirty_off && !e->table_all_dirty);
+  e->owed_bits = e->d_bits != nullptr;
+  if (e->owed_table_all) e->table_all_dirty = !e->own_table || e->table_exposed;  // (whoever holds the pointer may write it again)
+  if (!e->own_table || e->table_exposed) {
+    // a table somebody else can see: they may order their own work after the reset by the stream alone
+    const int rc = settle_table_on(e, e->stream);
+    if (rc != BC_OK) return rc;
   }
   e->bits_dirty = false;
   e->reads_since_fold = 0;
@@ -1364,6 +1535,10 @@ int bc_engine_counters(bc_engine* e, uint64_t out[BC_NCOUNTERS]) {
 void* bc_engine_table_ptr(bc_engine* e) {
   // whoever takes the pointer wants plain u32 counts behind it, now and after every later bc_engine_sync (two-level
   // counting: fold what is pending, and wait; from here on every sync folds)
+  if (hipSetDevice(e->device) != hipSuccess || settle_owed(e) != BC_OK) {
+    set_error(std::string("bc_engine_table_ptr: the pending reset of the table could not be run: ") + get_error());
+    return nullptr;
+  }
   e->table_exposed = true;
   e->table_all_dirty = true;
   if (e->bits_dirty && hipSetDevice(e->device) == hipSuccess && fold_bits(e) == BC_OK) (void)hipStreamSynchronize(e->stream);
@@ -1374,6 +1549,10 @@ void* bc_engine_table_ptr(bc_engine* e) {
 // table is not marked as exposed for good -- only the next reset has to zero all of it (the exchange writes the sum
 // into the root's table without flagging blocks).
 void* bc_internal_table_folded(bc_engine* e) {
+  if (hipSetDevice(e->device) != hipSuccess || settle_owed(e) != BC_OK) {
+    set_error(std::string("the pending reset of the table could not be run: ") + get_error());
+    return nullptr;
+  }
   if (e->bits_dirty && hipSetDevice(e->device) == hipSuccess && fold_bits(e) == BC_OK) (void)hipStreamSynchronize(e->stream);
   e->table_all_dirty = true;
   counts_changed(e);
@@ -1382,6 +1561,11 @@ void* bc_internal_table_folded(bc_engine* e) {
 // ... or as it stands, with the bit map beside it (*bits: NULL when nothing is pending there): the exchange packs
 // table + bit itself.  The caller says when the table has been overwritten with plain counts (the root: the job's sum).
 void* bc_internal_table_unfolded(bc_engine* e, const void** bits) {
+  *bits = nullptr;
+  if (hipSetDevice(e->device) != hipSuccess || settle_owed(e) != BC_OK) {
+    set_error(std::string("the pending reset of the table could not be run: ") + get_error());
+    return nullptr;
+  }
   *bits = e->bits_dirty ? e->d_bits : nullptr;
   e->table_all_dirty = true;
   counts_changed(e);
@@ -1389,6 +1573,10 @@ void* bc_internal_table_unfolded(bc_engine* e, const void** bits) {
 }
 int bc_internal_table_now_plain(bc_engine* e) {
   counts_changed(e);  // (the exchange has written the job's sum into the table)
+  {
+    const int rc = settle_owed(e);
+    if (rc != BC_OK) return rc;
+  }
   if (e->d_bits) HIP_TRY(hipMemsetAsync(e->d_bits, 0, e->n_bit_words * 4, e->stream));
   e->bits_dirty = false;
   e->reads_since_fold = 0;
@@ -2252,6 +2440,10 @@ int bc_engine_materialize_table(bc_engine* e) {
   }
   HIP_TRY(hipSetDevice(e->device));
   counts_changed(e);
+  {
+    const int rc = settle_owed(e);
+    if (rc != BC_OK) return rc;
+  }
   HIP_TRY(hipMemsetAsync(e->d_table, 0, e->table_entries * 4, e->stream));
   if (e->d_slots) {
     hipLaunchKernelGGL(set_to_table_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->n_slots,

@@ -12,6 +12,11 @@
 // then meet on the same quarter: there the first entry of a tuple in an item also sets its bit in memory, with a
 // returning atomicOr, and a bit another item had set meanwhile was not a first occurrence after all (table + 1).
 // Exactly one of them sets each bit; only the sole item of a bucket writes its quarters back whole.
+//
+// A fold onto a map that is known to be all zero but has not been written so (`fresh`: the engine's first fold after a
+// reset, bc_engine.hip) reads none of it: the sole item of a bucket starts its quarters from zeroed LDS and writes them
+// back whole as ever, and bc_fold_zero_unowned, between scan and apply, writes zeros over the buckets that have no sole
+// item -- the empty ones, and the split ones, whose items meet in memory.  Every word of the map is defined afterwards.
 #pragma once
 
 namespace bc {
@@ -146,11 +151,39 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_scatter(const uint32_t* __re
   }
 }
 
-// n_words: bit-map words in use (ceil(entries / 32)); dirty: the table's dirty-block map, or null
+// a fresh fold: zeroes the bit-map words (clipped to n_words) of every bucket that does not have exactly one apply item;
+// one (bucket, quarter) per workgroup and step
+__global__ __launch_bounds__(kFoldTPB) void bc_fold_zero_unowned(uint32_t nb, const uint32_t* __restrict__ item_off,
+                                                                uint32_t* __restrict__ bits, uint64_t n_words) {
+  constexpr uint32_t kPer = kFoldQuarterWords / 4u / kFoldTPB;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t p = blockIdx.x; p < nb * kFoldQuarters; p += gridDim.x) {
+    const uint32_t b = p / kFoldQuarters, quarter = p % kFoldQuarters;
+    if (item_off[b + 1] - item_off[b] == 1u) continue;
+    const uint64_t w0 = ((uint64_t)b << (kFoldBucketShift - 5)) + (uint64_t)quarter * kFoldQuarterWords;
+    if (w0 >= n_words) continue;
+    const uint64_t nw = n_words - w0 < kFoldQuarterWords ? n_words - w0 : kFoldQuarterWords;
+    uint32_t* gw = bits + w0;
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; ++k) {
+      const uint32_t w = (k * kFoldTPB + threadIdx.x) * 4u;
+      if (w + 4u <= nw) {
+        reinterpret_cast<uint4*>(gw)[w / 4u] = zero;
+      } else {
+        if (w + 0u < nw) gw[w + 0u] = 0u;
+        if (w + 1u < nw) gw[w + 1u] = 0u;
+        if (w + 2u < nw) gw[w + 2u] = 0u;
+      }
+    }
+  }
+}
+
+// n_words: bit-map words in use (ceil(entries / 32)); dirty: the table's dirty-block map, or null; fresh: the map counts
+// as all zero whatever memory holds (the owner of a bucket does not load it; bc_fold_zero_unowned has run)
 __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __restrict__ grouped, uint32_t nb,
                                                          const uint32_t* __restrict__ start, const uint32_t* __restrict__ item_off,
                                                          uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ table,
-                                                         uint8_t* __restrict__ dirty) {
+                                                         uint8_t* __restrict__ dirty, uint32_t fresh) {
   extern __shared__ uint32_t fold_smem[];
   uint4* q4 = reinterpret_cast<uint4*>(fold_smem);
   const uint32_t tid = threadIdx.x;
@@ -180,7 +213,9 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
       for (uint32_t k = 0; k < kPer; ++k) {
         const uint32_t w = (k * kFoldTPB + tid) * 4u;
         uint4 v;
-        if (w + 4u <= nw) {
+        if (fresh && owner) {
+          v = make_uint4(0u, 0u, 0u, 0u);
+        } else if (w + 4u <= nw) {
           v = reinterpret_cast<const uint4*>(gw)[w / 4u];
         } else {
           v.x = w + 0u < nw ? gw[w + 0u] : 0u;
@@ -244,17 +279,20 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
 // log: n entries; grouped: room for n; meta: [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each, with
 // cnt all zero (the fold leaves it so); nb: buckets (ceil(entries / 2^22), at most kFoldMaxBuckets); n_words: bit-map
 // words in use; dirty: the table's dirty-block map, or null.  scatter_grid / apply_grid: 0 = sized from n_cus as the
-// engine does; tests force other counts to vary how tiles and items interleave.
+// engine does; tests force other counts to vary how tiles and items interleave.  fresh: the bit map counts as all zero
+// and is not read (see the top of the file); every one of its n_words words is written.  have_cnt: cnt already holds
+// the entries per bucket (whoever wrote the log counted them): bc_fold_hist is skipped.
 inline hipError_t fold_launch(hipStream_t stream, const uint32_t* log, uint64_t n, uint32_t* grouped, uint32_t* meta,
                               uint32_t nb, uint32_t* bits, uint64_t n_words, uint32_t* table, uint8_t* dirty, uint32_t n_cus,
-                              uint32_t scatter_grid = 0, uint32_t apply_grid = 0) {
+                              uint32_t scatter_grid = 0, uint32_t apply_grid = 0, bool fresh = false,
+                              bool have_cnt = false) {
   uint32_t* cnt = meta;
   uint32_t* start = cnt + kFoldMaxBuckets + 1;
   uint32_t* cursor = start + kFoldMaxBuckets + 1;
   uint32_t* item_off = cursor + kFoldMaxBuckets + 1;
   const uint64_t hist_cap = 4ull * n_cus, hist_want = (n / 4 + kFoldTPB - 1) / kFoldTPB + 1;
   const uint64_t hist_grid = hist_want < hist_cap ? hist_want : hist_cap;
-  hipLaunchKernelGGL(bc_fold_hist, dim3((uint32_t)hist_grid), dim3(kFoldTPB), 0, stream, log, n, nb, cnt);
+  if (!have_cnt) hipLaunchKernelGGL(bc_fold_hist, dim3((uint32_t)hist_grid), dim3(kFoldTPB), 0, stream, log, n, nb, cnt);
   hipLaunchKernelGGL(bc_fold_scan, dim3(1), dim3(kFoldTPB), 0, stream, cnt, nb, start, cursor, item_off);
   hipError_t rc = hipFuncSetAttribute((const void*)bc_fold_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFoldScatterLds);
   if (rc != hipSuccess) return rc;
@@ -263,10 +301,15 @@ inline hipError_t fold_launch(hipStream_t stream, const uint32_t* log, uint64_t 
   const uint64_t tiles = (n + kFoldTile - 1) / kFoldTile, scatter_cap = 2ull * n_cus;
   if (!scatter_grid) scatter_grid = (uint32_t)(tiles < scatter_cap ? tiles : scatter_cap);
   hipLaunchKernelGGL(bc_fold_scatter, dim3(scatter_grid), dim3(kFoldTPB), kFoldScatterLds, stream, log, n, nb, cursor, grouped);
+  if (fresh) {
+    const uint32_t pairs = nb * kFoldQuarters, zero_cap = 4u * n_cus;
+    hipLaunchKernelGGL(bc_fold_zero_unowned, dim3(pairs < zero_cap ? pairs : zero_cap), dim3(kFoldTPB), 0, stream, nb,
+                       (const uint32_t*)item_off, bits, n_words);
+  }
   const uint64_t items_max = (n + kFoldChunk - 1) / kFoldChunk + nb;
   if (!apply_grid) apply_grid = (uint32_t)(items_max < n_cus ? items_max : n_cus);
   hipLaunchKernelGGL(bc_fold_apply, dim3(apply_grid), dim3(kFoldTPB), kFoldApplyLds, stream, (const uint32_t*)grouped, nb,
-                     (const uint32_t*)start, (const uint32_t*)item_off, bits, n_words, table, dirty);
+                     (const uint32_t*)start, (const uint32_t*)item_off, bits, n_words, table, dirty, fresh ? 1u : 0u);
   return hipGetLastError();
 }
 
