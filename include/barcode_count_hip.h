@@ -248,6 +248,39 @@ int bc_engine_render_enriched(bc_engine *e, int kind, uint32_t sample_idx, bc_te
 int bc_engine_render_enriched_merged(bc_engine *e, int kind, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn,
                                      void *user, uint64_t *n_rows);
 
+/* The counts files of a raw-key plan (bc_plan_mode 2: some counted barcode has no conversion file, so its capture is
+ * the key) as CSV text, written on the device from the counts bc_engine_finish would hand out now: the submits waited
+ * for, a random-barcode plan's key set aggregated into per-tuple distinct counts, the root's merged map after
+ * bc_engine_finish_all.  The map, the counters and the rows stay as they are; the calls may come before or after
+ * bc_engine_finish, and more than once.
+ * Layout, with G = the number of counted barcodes; field f_g = the ID (bc_plan_counted_id), copied byte for byte, when
+ * barcode g has a known set, else the capture's bases as they were read (A, C, T, G, N):
+ *   bc_engine_render_raw_counts: for sample index s (0 for a plan without a sample group) one line per tuple the sample
+ *     counts:  f_0,f_1,..,f_{G-1},count\n
+ *   bc_engine_render_raw_merged: for the ordered list sample_idx[0 .. n_samples) (a sample may come twice; any order)
+ *     one line per tuple for which some LISTED sample counts:  f_0,..,f_{G-1},c_0,c_1,..\n  with c_k the count of sample
+ *     sample_idx[k], 0 written as "0".
+ * Order: lines ascend by the tuple (d_0, .., d_{G-1}) compared barcode by barcode, Barcode_1 first; d_g is the index
+ * into the set for a known barcode and, for a raw one, the number  sum_k c_k * 5^k  over its bases with A, C, T, G, N =
+ * 0 .. 4 and k the base's position from 0 (so captures compare from their LAST base backwards).  The order is made by a
+ * radix sort on the device (24.5 bytes per row while it runs), and the text is the same on every run.  No header line.
+ * The sorted rows stay on the device, 12 bytes per key the map may hold, until something changes what bc_engine_finish
+ * would hand out (a submit, a reset, a key or count import, bc_engine_clear_keys, the exchange of bc_engine_finish_all):
+ * the renders of one state of the counts share one sort.
+ * Chunking, BC_RENDER_CHUNK_BYTES, the callback contract (`fn` != 0 -> BC_ERR_STATE, the engine still usable) and
+ * BC_ERR_NOMEM are those of bc_engine_render_counts.
+ * BC_ERR_UNSUPPORTED: a dense plan (use bc_engine_render_counts / _merged); a plan with wide keys
+ * (bc_engine_key_words() > 1) or whose SAMPLE barcode is kept raw (its sample keys are captures, not indices,
+ * info.rs:742-757) -- write those from bc_engine_finish + bc_engine_row_text on the host.  BC_ERR_INVALID: a sample index
+ * out of range, a null callback, a null list with n_samples != 0. */
+int bc_engine_render_raw_counts(bc_engine *e, uint32_t sample_idx, bc_text_fn fn, void *user, uint64_t *n_rows);
+int bc_engine_render_raw_merged(bc_engine *e, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn, void *user,
+                                uint64_t *n_rows);
+/* How many sorts the engine has made for those renders since it was created.  Read-only: does not wait for the device. */
+int bc_engine_raw_render_sorts(const bc_engine *e, uint64_t *n);
+/* Device time of the last of them (export of the map, re-key, sort), in milliseconds, from HIP events; 0 before any. */
+int bc_engine_raw_render_sort_ms(const bc_engine *e, double *ms);
+
 /* Row i as the reference's Results holds it (info.rs:661-665): the sample key (a sample barcode
  * sequence, or "barcode" without a sample group) and the counted barcodes "b1,b2,.." as sequences.
  * Works for every plan, including those that keep raw captures (no sample / counted-barcode

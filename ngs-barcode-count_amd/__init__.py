@@ -334,6 +334,33 @@ class Engine:
         return self._render(lambda fn, n: self._lib.bc_engine_render_merged(
             self._e, cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
 
+    def render_raw_counts(self, sample=0, on_text=None):
+        """bc_engine_render_raw_counts: the lines of sample index `sample`'s counts file (no header) of a raw-key plan,
+        sorted and written on the device: b"f_0,..,f_{G-1},count\\n" per tuple the sample counts, a field being the ID of
+        a known barcode or the bases of a raw capture; lines ascend by the tuple of per-barcode digits (set index, or the
+        capture's base-5 code with its first base least significant).  Returns as render_counts does."""
+        return self._render(lambda fn, n: self._lib.bc_engine_render_raw_counts(self._e, int(sample), fn, None, n), on_text)
+
+    def render_raw_merged(self, samples, on_text=None):
+        """bc_engine_render_raw_merged: the merged file's lines (no header) of a raw-key plan for the sample indices
+        `samples` as columns, in that order: one line per tuple that counts in any LISTED sample, zero counts written as 0."""
+        cols = np.ascontiguousarray(list(samples), dtype=np.uint32)
+        return self._render(lambda fn, n: self._lib.bc_engine_render_raw_merged(
+            self._e, cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
+
+    def raw_render_sorts(self):
+        """sorts made for render_raw_counts() / render_raw_merged() since the engine was created: the renders of one state
+        of the counts share one"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_raw_render_sorts(self._e, C.byref(n)))
+        return n.value
+
+    def raw_render_sort_ms(self):
+        """device milliseconds of the last of those sorts (map export, re-key, sort)"""
+        v = C.c_double()
+        _check(self._lib, self._lib.bc_engine_raw_render_sort_ms(self._e, C.byref(v)))
+        return v.value
+
     def render_enriched(self, kind, sample=0, on_text=None):
         """bc_engine_render_enriched: the lines of sample index `sample`'s Single (kind = ENRICH_SINGLE) or Double
         (ENRICH_DOUBLE) file (no header), written on the device in ascending key order: G comma-joined fields of which

@@ -283,6 +283,9 @@ struct Run {
   bool device_writers = false;
   // ... and the Single / Double files (bc_engine_render_enriched / _merged): no single_hash / double_hash at all
   bool device_enrich = false;
+  // a raw-key plan's full-counts files sorted and written on the device (bc_engine_render_raw_counts / _merged;
+  // BC_DEVICE_RAW_WRITERS=1): no rows on the host either
+  bool raw_writers = false;
   std::unordered_map<std::string, uint32_t> sample_index;  // sample key -> the engine's sample index
 };
 
@@ -554,6 +557,9 @@ uint64_t render_file(Run& r, const std::string& name, const std::string& head, c
   if (enriched)
     rc = merged ? bc_engine_render_enriched_merged(r.engine, enriched, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
                 : bc_engine_render_enriched(r.engine, enriched, cols[0], text_to_file, f, &n);
+  else if (r.raw_writers)
+    rc = merged ? bc_engine_render_raw_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
+                : bc_engine_render_raw_counts(r.engine, cols[0], text_to_file, f, &n);
   else
     rc = merged ? bc_engine_render_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
                 : bc_engine_render_counts(r.engine, cols[0], text_to_file, f, &n);
@@ -638,6 +644,7 @@ uint64_t render_sample_file(Run& r, const std::string& sample, const std::string
 
 void write_counts_files(Run& r) {  // output.rs:74-181
   auto samples = ordered_samples(r, r.sample_keys);
+  const bool device_text = r.device_writers || r.raw_writers;  // the full-counts files come from a device renderer
   if (r.args.enrich && !r.device_enrich)
     for (const auto& k : samples) {  // ResultsEnrichment::add_sample_barcodes, info.rs:829-837
       r.single_hash[k];
@@ -658,7 +665,7 @@ void write_counts_files(Run& r) {  // output.rs:74-181
     const std::string file_name = r.args.prefix + "_" + sample_name(r, sb) + "_counts.csv";
     printf("%s\n", file_name.c_str());
     r.output_files.push_back(file_name);
-    if (r.device_writers) {
+    if (device_text) {
       r.output_counts.push_back(render_sample_file(r, sb, file_name, header));
       continue;
     }
@@ -671,14 +678,14 @@ void write_counts_files(Run& r) {  // output.rs:74-181
   if (r.args.merge_output) {
     const std::string merged = r.args.prefix + "_counts.all.csv";
     printf("%s\n", merged.c_str());
-    if (r.device_writers) {  // the columns in the header's order; a row per tuple that counts in any of them
+    if (device_text) {  // the columns in the header's order; a row per tuple that counts in any of them
       std::vector<uint32_t> cols;
       for (const auto& sb : samples) cols.push_back(r.sample_index.at(sb));
       r.merged_count = render_file(r, merged, r.merge_text, cols, true);
     }
     printf("Barcodes counted: %s\n", commas(r.merged_count).c_str());
     r.output_files.push_back(merged);
-    if (!r.device_writers) write_file(r, merged, r.merge_text);
+    if (!device_text) write_file(r, merged, r.merge_text);
     r.merge_text.clear();
     r.output_counts.insert(r.output_counts.begin(), r.merged_count);  // output.rs:171 (the file name went to the back)
     r.merged_count = 0;
@@ -938,13 +945,36 @@ int main(int argc, char** argv) {
       n_rows = 0;  // (no row is read below)
     }
   }
+  // Raw-key plans (some counted barcode has no conversion file): with BC_DEVICE_RAW_WRITERS=1 the full-counts files are
+  // sorted and rendered on the device from the key map (bc_engine_render_raw_counts / _merged), which may change the
+  // order of the lines in those files and nothing else.  Kept on the rows: wide keys, a sample barcode kept raw (its
+  // samples are captures), enrichment (it needs the rows' strings), a counted file that names only some of the
+  // barcodes, and a sample file next to a scheme without a sample group (as above).
+  const bool raw_plan = bc_plan_mode(r.plan) == 2;
+  if (raw_plan) {
+    const char* rw = getenv("BC_DEVICE_RAW_WRITERS");
+    bool counted_whole = true;  // the counted file is absent, or names every counted barcode
+    for (const auto& set : r.counted) counted_whole = counted_whole && !set.empty();
+    r.raw_writers = rw && strcmp(rw, "1") == 0 && bc_engine_key_words(r.engine) == 1 && (!sample_group || !r.samples.empty()) &&
+                    (sample_group || r.samples.empty()) && !r.args.enrich && counted_whole;
+    if (r.raw_writers) {
+      if (sample_group)
+        for (uint32_t i = 0; i < r.samples.size(); ++i) r.sample_index[r.samples[i].first] = i;
+      else
+        r.sample_index["barcode"] = 0;
+      n_rows = 0;  // (no row is read below)
+    }
+  }
   if (getenv("BC_WRITERS_VERBOSE"))  // (which path writes the full-counts files; tests assert it)
     fprintf(stderr, "[barcode-count] writers: %s\n",
             r.device_writers ? "device text (bc_engine_render_counts)" : "per-row strings");
   if (r.args.enrich && getenv("BC_WRITERS_VERBOSE"))  // (... and the Single / Double files)
     fprintf(stderr, "[barcode-count] enrichment writers: %s\n",
             r.device_enrich ? "device text (bc_engine_render_enriched)" : "per-row strings");
-  if (!multi && !r.device_writers && bc_engine_finish(r.engine, &n_rows)) die("%s", bc_last_error());
+  if (raw_plan && getenv("BC_WRITERS_VERBOSE"))  // (... of a raw-key plan)
+    fprintf(stderr, "[barcode-count] raw writers: %s\n",
+            r.raw_writers ? "device text (bc_engine_render_raw_counts)" : "per-row strings");
+  if (!multi && !r.device_writers && !r.raw_writers && bc_engine_finish(r.engine, &n_rows)) die("%s", bc_last_error());
   r.counted_map.resize(r.counted.size());
   for (size_t b = 0; b < r.counted.size(); ++b)
     for (const auto& kv : r.counted[b]) r.counted_map[b][kv.first] = kv.second;
@@ -959,8 +989,8 @@ int main(int argc, char** argv) {
     it->second.push_back({code, written, cnt});
     if (r.args.merge_output) r.results_map[key][code] = cnt;
   };
-  if (r.device_writers) {
-    // nothing to rebuild: the writers read the table
+  if (r.device_writers || r.raw_writers) {
+    // nothing to rebuild: the writers read the table (the sorted key map)
   } else if (dense) {
     // dense plan: rows come as indices into the known sets; the sequence / ID strings are looked up
     const uint32_t nb = r.barcode_num ? r.barcode_num : 1;

@@ -24,6 +24,8 @@
 #include "bc_enrich.h"
 #include "bc_render.h"
 #include "bc_enrich_render.h"
+#include "bc_raw_render.h"
+#include "bc_sort.h"
 #include "bc_fold.h"
 #include "bc_jit.h"
 #include "bc_plan.hpp"
@@ -676,6 +678,15 @@ struct bc_engine {
   uint64_t sums_passes = 0;              // table passes made for them since the engine was created
   bool canon_ready = false;              // the canonical maps of the label pool have been built
   uint32_t* d_canon = nullptr;           // canon[off_g + i]; NULL when no set shares an ID
+  // The raw-key renderer (bc_raw_render.h): the map's (key, count) pairs, re-keyed and sorted (bc_sort.h), kept on the
+  // device for the counts of epoch raw_epoch -- the S + 1 renders of one merged run sort once.  Whatever moves
+  // counts_epoch (submits, imports, resets, clear_keys, finish_all) retires them; the next render frees and rebuilds.
+  uint64_t raw_epoch = 0;
+  uint64_t* d_raw_keys = nullptr;
+  uint32_t* d_raw_cnts = nullptr;
+  uint64_t raw_n = 0;
+  uint64_t raw_sorts = 0;                // sorts made since the engine was created (bc_engine_raw_render_sorts)
+  float raw_sort_ms = 0.f;               // export + re-key + sort of the last one, from HIP events
 };
 
 static void counts_changed(bc_engine* e) { ++e->counts_epoch; }
@@ -713,6 +724,8 @@ static void engine_free(bc_engine* e) {
   if (e->d_vals) (void)hipFree(e->d_vals);
   if (e->d_ready) (void)hipFree(e->d_ready);
   if (e->d_sums) (void)hipFree(e->d_sums);
+  if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
+  if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
   if (e->d_counters) (void)hipFree(e->d_counters);
   if (e->d_plan) (void)hipFree(e->d_plan);
   if (e->reset_stream) (void)hipStreamSynchronize(e->reset_stream);
@@ -2087,6 +2100,18 @@ static hipError_t text_write(const bc::EnrichRenderView& v, uint64_t b0, uint64_
   return bc_enrich_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
 }
 
+static hipError_t text_sizes(const bc::RawRenderView& v, uint64_t nb, uint32_t* d_rows, unsigned long long* d_bytes, hipStream_t st) {
+  return bc_raw_render_sizes_launch(v, nb, d_rows, d_bytes, st);
+}
+static hipError_t text_lens(const bc::RawRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t st) {
+  return bc_raw_render_lens_launch(v, lo, n, d_len, st);
+}
+static hipError_t text_write(const bc::RawRenderView& v, uint64_t b0, uint64_t nb, uint64_t lo, uint64_t hi,
+                             const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
+                             uint64_t out_cap, hipStream_t st) {
+  return bc_raw_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
+}
+
 // The lines of the keys [0, n_keys) that have one, in ascending key order, handed to `fn` in chunks that end with a
 // line.  Pass 1 sizes every block of the key space, the host scans the sizes and cuts the space into ranges whose text
 // fits one staging buffer, pass 2 writes range after range into one of two buffers (device + pinned) while the host hands
@@ -2290,6 +2315,201 @@ int bc_engine_render_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, vo
 int bc_engine_render_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
                             uint64_t* n_rows) {
   return render_text(e, "bc_engine_render_merged", sample_idx, n_samples, fn, user, n_rows);
+}
+
+// ---- counts of a raw-key plan as text (bc_raw_render.h / bc_raw_render.hip, bc_sort.h) ----
+
+static void raw_sorted_drop(bc_engine* e) {
+  if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
+  if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
+  e->d_raw_keys = nullptr;
+  e->d_raw_cnts = nullptr;
+  e->raw_n = 0;
+  e->raw_epoch = 0;
+}
+
+// The pairs of the current counts, sorted into the order of the files, in e->d_raw_keys / d_raw_cnts (raw_n of them):
+// served as they are while the counts epoch stands, else exported from the map (a random-barcode plan's key set first
+// aggregated into per-tuple distinct counts, as finish_sparse does), re-keyed and sorted.  Device memory while it runs:
+// the map's export bound x 12 bytes (kept), the same again for the sort's other buffers and n / 2 bytes of histograms.
+static int ensure_raw_sorted(bc_engine* e, uint64_t t_space, uint32_t S) {
+  if (e->raw_epoch == e->counts_epoch) return BC_OK;
+  const DevPlan& P = e->h.plan;
+  raw_sorted_drop(e);
+  if (!e->d_slots) {  // nothing was ever submitted or imported
+    e->raw_epoch = e->counts_epoch;
+    return BC_OK;
+  }
+  ScratchGuard g;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIP_TRY(hipEventCreate(&ev0));
+  g.events.push_back(ev0);
+  HIP_TRY(hipEventCreate(&ev1));
+  g.events.push_back(ev1);
+  HIP_TRY(hipEventRecord(ev0, e->stream));
+  unsigned long long* keys = e->d_slots;
+  uint32_t* vals = e->d_vals;
+  const uint64_t n_slots = e->n_slots;
+  if (P.has_random) {
+    // count of a tuple = number of its distinct random barcodes (output.rs:265-270)
+    unsigned long long* agg_keys = nullptr;
+    uint32_t* agg_vals = nullptr;
+    HIP_TRY(g.dmalloc(&agg_keys, n_slots * 8));
+    HIP_TRY(g.dmalloc(&agg_vals, n_slots * 4));
+    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, agg_keys, n_slots);
+    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
+    hipLaunchKernelGGL(set_to_map_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, n_slots, P.rspace,
+                       agg_keys, agg_vals, n_slots - 1);
+    HIP_TRY(hipGetLastError());
+    keys = agg_keys;
+    vals = agg_vals;
+  }
+  unsigned long long* d_n = nullptr;
+  uint64_t* d_key = nullptr;
+  uint32_t* d_cnt = nullptr;
+  HIP_TRY(g.dmalloc(&d_n, 8));
+  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
+  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);  // upper bound on the rows: the keys held
+  HIP_TRY(g.dmalloc(&d_key, cap * 8));
+  HIP_TRY(g.dmalloc(&d_cnt, cap * 4));
+  hipLaunchKernelGGL(map_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, vals, n_slots, d_n, d_key, d_cnt);
+  HIP_TRY(hipGetLastError());
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (n > cap) {  // (cannot happen: key_bound counts every insert)
+    set_error("raw render: the key map holds more keys than its bound");
+    return BC_ERR_STATE;
+  }
+  if (n) {
+    uint64_t* d_key2 = nullptr;
+    uint32_t *d_cnt2 = nullptr, *d_scratch = nullptr;
+    HIP_TRY(g.dmalloc(&d_key2, n * 8));
+    HIP_TRY(g.dmalloc(&d_cnt2, n * 4));
+    HIP_TRY(g.dmalloc(&d_scratch, bc::sort_scratch_words(n) * 4));
+    HIP_TRY(bc_raw_rekey_launch(d_key, n, t_space, S, e->stream));
+    uint32_t key_bits = 1;  // the bit length of the largest key of the space (the re-keyed digits have the same radices)
+    while (key_bits < 64 && ((e->h.table_entries - 1) >> key_bits) != 0) ++key_bits;
+    const hipError_t src = bc::sort_pairs_launch(e->stream, d_key, d_cnt, d_key2, d_cnt2, n, key_bits, d_scratch);
+    if (src == hipErrorInvalidValue) {
+      set_error("raw render: " + std::to_string(n) + " rows pass what one sort takes (2^32); write them from bc_engine_row_text on the host");
+      return BC_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(src);
+  }
+  HIP_TRY(hipEventRecord(ev1, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  (void)hipEventElapsedTime(&e->raw_sort_ms, ev0, ev1);
+  for (void* keep : {(void*)d_key, (void*)d_cnt}) g.dev.erase(std::find(g.dev.begin(), g.dev.end(), keep));
+  e->d_raw_keys = d_key;
+  e->d_raw_cnts = d_cnt;
+  e->raw_n = n;
+  e->raw_epoch = e->counts_epoch;
+  ++e->raw_sorts;
+  return BC_OK;
+}
+
+static int render_raw(bc_engine* e, const char* who, bool merged, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
+                      void* user, uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (!P.sparse) {
+    set_error(std::string(who) + ": the plan has a dense table: its files come from bc_engine_render_counts / "
+              "bc_engine_render_merged");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->key_words > 1) {
+    set_error(std::string(who) + ": the plan's keys are " + std::to_string(e->key_words) +
+              " words wide; write its rows from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
+    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: write the rows "
+              "from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (!fn || (n_cols && !cols)) {
+    set_error(std::string(who) + ": null callback or sample list");
+    return BC_ERR_INVALID;
+  }
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  const uint32_t S = g0 ? P.groups[0].n_refs : 1u;
+  const uint64_t t_space = g0 ? P.groups[0].table_stride : e->h.table_entries;
+  for (uint32_t c = 0; c < n_cols; ++c)
+    if (cols[c] >= S) {
+      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
+      return BC_ERR_INVALID;
+    }
+  bc::RawRenderView v;
+  memset(&v, 0, sizeof v);
+  v.G = e->barcode_num;
+  v.S = S;
+  v.merged = merged ? 1u : 0u;
+  v.sample = n_cols ? cols[0] : 0u;
+  v.n_cols = n_cols;
+  if (v.G > (uint32_t)bc::kRenderMaxG || g0 + v.G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
+    set_error(std::string(who) + ": the plan's groups do not fit the view");
+    return BC_ERR_STATE;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = bc_engine_sync(e);  // the submits, as bc_engine_finish waits for them
+  if (rc) return rc;
+  if ((rc = ensure_raw_sorted(e, t_space, S)) != BC_OK) return rc;
+  if (n_cols == 0 || e->raw_n == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    const DevGroup& G = P.groups[g0 + g];
+    if (G.mode == kSetNone) {
+      v.raw_len[g] = G.len;
+      v.radix[g] = 1;
+      for (uint32_t k = 0; k < G.len; ++k) v.radix[g] *= 5;
+      max_line += G.len;
+    } else {
+      if (bc_plan_n_counted(e->src_plan, g) != G.n_refs) {  // (cannot happen: the key's digits are the plan's sets)
+        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+        return BC_ERR_STATE;
+      }
+      v.radix[g] = G.n_refs;
+      v.off_start[g] = e->label_off_start[g];
+      max_line += e->label_max[g];
+    }
+  }
+  if (max_line > bc::kRenderMaxLine) {
+    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
+              std::to_string(bc::kRenderMaxLine));
+    return BC_ERR_UNSUPPORTED;
+  }
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
+  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
+  v.keys = e->d_raw_keys;
+  v.cnts = e->d_raw_cnts;
+  v.n = e->raw_n;
+  v.cols = d_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+int bc_engine_render_raw_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_raw(e, "bc_engine_render_raw_counts", false, &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_raw_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
+                                uint64_t* n_rows) {
+  return render_raw(e, "bc_engine_render_raw_merged", true, sample_idx, n_samples, fn, user, n_rows);
+}
+
+int bc_engine_raw_render_sorts(const bc_engine* e, uint64_t* n) {
+  *n = e->raw_sorts;
+  return BC_OK;
+}
+
+int bc_engine_raw_render_sort_ms(const bc_engine* e, double* ms) {
+  *ms = (double)e->raw_sort_ms;
+  return BC_OK;
 }
 
 // ---- Single / Double enrichment as text (bc_enrich_render.h / bc_enrich_render.hip) ----

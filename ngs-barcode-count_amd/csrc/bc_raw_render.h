@@ -1,0 +1,207 @@
+// bc_raw_render.h -- the text of a raw-key plan's counts files (bc_engine_render_raw_counts / bc_engine_render_raw_merged):
+// the lane-level pieces, shared by the kernels of bc_raw_render.hip and the host harness
+// tests/render/raw_render_host.cpp (which runs this SAME code under AddressSanitizer; never a product path on the host).
+//
+// A raw-key plan (bc_plan_mode() == 2) keeps some capture as it was read, so its rows have no table index; what the
+// device holds is a map of (key, count).  A key is a mixed-radix number over the scheme's groups: a known set gives its
+// index (radix: the set's size), a raw capture its base-5 code  sum c_k 5^k  with A, C, T, G, N = 0 .. 4 and k the base's
+// position (radix 5^len; the FIRST base is the least significant).
+//
+// The order of the lines.  Lines ascend by the tuple of the counted groups' digits, compared group by group in scheme
+// order (Barcode_1 first); a digit is the set index of a known group and the base-5 code above of a raw one.  A per-
+// sample file holds the tuples counted for that sample in that order, the merged file every tuple counted for some
+// listed sample, once.  (Two raw captures therefore compare by their LAST differing base, in the order A < C < T < G < N.)
+//
+// How the order is made: the exported keys are re-keyed to  T * S + s  (T: the tuple's mixed-radix number, first counted
+// group most significant; s: the sample index, S the number of samples, or S = 1 and s = 0 without a sample group) and
+// sorted with their counts (bc_sort.h).  The view below reads that sorted array.  A "key index" of the text kernels is a
+// position i in it:
+//     per-sample view   position i has a line when its s is the view's sample
+//     merged view       position i has a line when it is the first of its run of equal T (the run has at most S entries,
+//                       ascending in s) and some listed sample counts; the lane looks its columns up in the run
+// and the line is
+//     f_0,f_1,..,f_{G-1},c_0,c_1,..\n
+// f_g: the ID of the set's entry, copied from the label pool (bc_render.h's) when group g is a known set, else the
+// capture's bases "ACTGN"[c_k], first base first;  c_k: the count of the column in decimal ("0" for a sample that does
+// not count the tuple; a sample may be listed twice, the list may be in any order).
+//
+// As in bc_render.h a line is measured and written from its END backwards, so no digit is ever kept in a local array;
+// inside a raw field the bases come out in ascending k, which is the order the code gives them up.
+#ifndef BC_RAW_RENDER_H
+#define BC_RAW_RENDER_H
+
+#include "bc_render.h"
+
+namespace bc {
+
+struct RawRenderView {
+  const uint64_t* keys;        // the sorted keys T * S + s
+  const uint32_t* cnts;        // their counts
+  const uint32_t* cols;        // sample index of every column (the per-sample view has one)
+  const uint32_t* label_off;   // the label pool, as RenderView's
+  const uint8_t* label_bytes;
+  uint64_t n;                  // entries of keys / cnts
+  uint32_t S;                  // samples: the radix of s
+  uint32_t n_cols;
+  uint32_t merged;             // 0: the per-sample view of cols[0] = sample
+  uint32_t sample;
+  uint32_t G;                  // counted groups
+  uint32_t raw_len[kRenderMaxG];    // bases of a raw group; 0: a known set
+  uint32_t off_start[kRenderMaxG];  // known set: where its offsets start in label_off
+  uint64_t radix[kRenderMaxG];      // the set's size, or 5^raw_len
+};
+
+// r -> its least significant digit of the given radix; r loses it
+BC_HD uint64_t raw_take_digit(uint64_t& r, uint64_t radix) {
+  if (((r | radix) >> 32) == 0) {
+    const uint32_t r32 = (uint32_t)r, n32 = (uint32_t)radix, q = r32 / n32;
+    r = q;
+    return r32 - q * n32;
+  }
+  const uint64_t q = r / radix;
+  const uint64_t d = r - q * radix;
+  r = q;
+  return d;
+}
+
+// "ACTGN"[d] without a table in memory
+BC_HD uint32_t raw_base_char(uint32_t d) { return (uint32_t)((0x4E47544341ull >> (8u * d)) & 0xFFu); }
+
+// the count of sample `s` for the tuple whose run starts at position i (0: the sample does not count it).  The run is
+// the at most S entries from i on with the same T, ascending in s: a binary search for T * S + s among them.
+BC_HD uint32_t raw_run_count(const RawRenderView& v, uint64_t i, uint64_t T, uint32_t s) {
+  const uint64_t want = T * v.S + s;
+  uint64_t lo = i, hi = i + v.S < v.n ? i + v.S : v.n;  // [lo, hi)
+  while (lo < hi) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (v.keys[mid] < want)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo < v.n && lo < i + v.S && v.keys[lo] == want ? v.cnts[lo] : 0u;
+}
+
+// Position i -> does it have a line at all, and its tuple number T.  (The count columns follow from raw_col_count.)
+BC_HD bool raw_has_line(const RawRenderView& v, uint64_t i, uint64_t& T) {
+  uint64_t r = v.keys[i];
+  const uint32_t s = (uint32_t)raw_take_digit(r, v.S);
+  T = r;
+  if (!v.merged) return s == v.sample;
+  if (i == 0) return true;
+  uint64_t p = v.keys[i - 1];
+  (void)raw_take_digit(p, v.S);
+  return p != T;
+}
+
+// column c of the line at position i
+BC_HD uint32_t raw_col_count(const RawRenderView& v, uint64_t i, uint64_t T, uint32_t c) {
+  return v.merged ? raw_run_count(v, i, T, v.cols[c]) : v.cnts[i];
+}
+
+// bytes of position i's line, '\n' included; 0: no line
+BC_HD uint32_t raw_row_len(const RawRenderView& v, uint64_t i) {
+  uint64_t T;
+  if (!raw_has_line(v, i, T)) return 0;
+  uint32_t any = 0, len = 1u + (v.G ? v.G - 1u : 0u);  // '\n' and the commas between the fields
+  for (uint32_t c = 0; c < v.n_cols; ++c) {
+    const uint32_t x = raw_col_count(v, i, T, c);
+    any |= x;
+    len += 1u + render_digits(x);  // ",count"
+  }
+  if (v.merged && !any) return 0;
+  uint64_t r = T;
+  for (uint32_t g = v.G; g-- > 0;) {
+    const uint64_t d = raw_take_digit(r, v.radix[g]);
+    if (v.raw_len[g]) {
+      len += v.raw_len[g];
+    } else {
+      const uint32_t* o = v.label_off + v.off_start[g] + (uint32_t)d;
+      len += o[1] - o[0];
+    }
+  }
+  return len;
+}
+
+// Writes the part of position i's line (len = raw_row_len, not 0) that falls into the window dst[0 .. win); the line
+// starts at window position `at`, which may be negative or beyond the window (render_row_write's contract).
+template <typename Byte>
+BC_HD void raw_row_write(const RawRenderView& v, uint64_t i, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
+  uint64_t T;
+  (void)raw_has_line(v, i, T);
+  int64_t p = at + (int64_t)len;  // one past the byte written next (the line is written backwards)
+#define BC_RAW_PUT(ch)                                    \
+  do {                                                    \
+    --p;                                                  \
+    if (p >= 0 && p < (int64_t)win) dst[p] = (Byte)(ch);  \
+  } while (0)
+  BC_RAW_PUT('\n');
+  for (uint32_t c = v.n_cols; c-- > 0;) {
+    uint32_t x = raw_col_count(v, i, T, c);
+    do {
+      const uint32_t q = x / 10u;  // (a multiplication: the divisor is a constant)
+      BC_RAW_PUT('0' + (x - q * 10u));
+      x = q;
+    } while (x);
+    BC_RAW_PUT(',');
+  }
+  uint64_t r = T;
+  for (uint32_t g = v.G; g-- > 0;) {
+    uint64_t d = raw_take_digit(r, v.radix[g]);
+    if (v.raw_len[g]) {
+      // the capture lies at [p - len, p): base k at p - len + k, and the code gives up base 0 first
+      const uint32_t n = v.raw_len[g];
+      p -= (int64_t)n;
+      for (uint32_t k = 0; k < n; ++k) {
+        uint32_t c5;
+        if ((d >> 32) == 0) {
+          const uint32_t d32 = (uint32_t)d, q = d32 / 5u;
+          c5 = d32 - q * 5u;
+          d = q;
+        } else {
+          const uint64_t q = d / 5u;
+          c5 = (uint32_t)(d - q * 5u);
+          d = q;
+        }
+        const int64_t w = p + (int64_t)k;
+        if (w >= 0 && w < (int64_t)win) dst[w] = (Byte)raw_base_char(c5);
+      }
+    } else {
+      const uint32_t* o = v.label_off + v.off_start[g] + (uint32_t)d;
+      const uint32_t a = o[0], n = o[1] - o[0];
+      int64_t lo = p - (int64_t)n, hi = p;
+      p = lo;
+      if (lo < 0) lo = 0;
+      if (hi > (int64_t)win) hi = (int64_t)win;
+      for (int64_t w = lo; w < hi; ++w) dst[w] = (Byte)v.label_bytes[a + (uint32_t)(w - p)];
+    }
+    if (g) BC_RAW_PUT(',');
+  }
+#undef BC_RAW_PUT
+}
+
+// the names bc_text_kernels.h reaches a view's lane code by
+BC_HD uint64_t text_keys(const RawRenderView& v) { return v.n; }
+BC_HD uint32_t text_line_len(const RawRenderView& v, uint64_t i) { return raw_row_len(v, i); }
+template <typename Byte>
+BC_HD void text_line_write(const RawRenderView& v, uint64_t i, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
+  raw_row_write(v, i, len, dst, at, win);
+}
+
+}  // namespace bc
+
+#if defined(__HIPCC__)
+// The kernels (bc_raw_render.hip); all enqueue on `stream`.
+// keys[i] = s * t_space + T  (the engine's key: the sample group, when there is one, is its most significant digit)
+//   ->  T * S + s,  in place; S == 1: nothing to do, and nothing is launched
+hipError_t bc_raw_rekey_launch(uint64_t* d_keys, uint64_t n, uint64_t t_space, uint32_t S, hipStream_t stream);
+// the three passes of bc_text_kernels.h for this view (bc_render.h describes them)
+hipError_t bc_raw_render_sizes_launch(const bc::RawRenderView& v, uint64_t n_blocks, uint32_t* d_rows,
+                                      unsigned long long* d_bytes, hipStream_t stream);
+hipError_t bc_raw_render_lens_launch(const bc::RawRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t stream);
+hipError_t bc_raw_render_write_launch(const bc::RawRenderView& v, uint64_t b0, uint64_t n_blocks, uint64_t lo, uint64_t hi,
+                                      const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
+                                      uint64_t out_cap, hipStream_t stream);
+#endif
+
+#endif

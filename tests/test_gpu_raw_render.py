@@ -1,0 +1,256 @@
+"""The counts files of raw-key plans as text from the device (bc_engine_render_raw_counts / bc_engine_render_raw_merged,
+csrc/bc_raw_render.h, the order made by csrc/bc_sort.h).  The expected text never comes from the renderer: it is built
+in Python from the engine's rows (bc_engine_finish + bc_engine_row_text), grouped by sample and ordered by the digit
+tuple computed from each row's own text (raw_render_cases.expected), and compared byte for byte."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import cases
+import readgen
+import raw_render_cases as rrc
+import raw_render_lib as rrl
+from test_gpu_parity import make_plan, run_device
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _pkg():
+    import ngs_barcode_count_amd as pkg
+    return pkg
+
+
+def run(c):
+    plan = make_plan(c)
+    seq, qual, lens = readgen.to_arrays(c["reads"])
+    eng, _, _ = run_device(plan, seq, qual, lens, seq.shape[1], seq.shape[1])
+    return eng
+
+
+def key_words(eng):
+    return eng._lib.bc_engine_key_words(eng._e)
+
+
+def n_samples_of(plan):
+    return len(plan.samples()) if plan.sample_barcode else 1
+
+
+def check_engine(eng, scheme, merged_orders):
+    plan = eng.plan
+    rows = eng.result_rows()
+    texts = {}
+    for s in range(n_samples_of(plan)):
+        texts[s] = eng.render_raw_counts(s)
+        assert texts[s] == rrc.expected(plan, scheme, rows, [s], False), s
+    for cols in merged_orders:
+        assert eng.render_raw_merged(cols) == rrc.expected(plan, scheme, rows, cols, True), cols
+    return rows, texts
+
+
+_DEL = {}
+
+
+def del_engine():
+    """the DEL raw-key engine, its rows and its per-sample texts: made once, shared, never changed"""
+    if not _DEL:
+        c = rrc.del_raw_case()
+        eng = run(c)
+        _DEL.update(case=c, eng=eng, rows=eng.result_rows(), sorts0=eng.raw_render_sorts())
+    return _DEL
+
+
+def test_raw_counted_case():
+    c = cases.build_case("raw_counted", seed=29, n=4000)
+    eng = run(c)
+    assert eng.plan.mode == "sparse" and key_words(eng) == 1
+    before = eng.render_raw_counts(0)  # before any finish
+    rows, texts = check_engine(eng, c["scheme"], [[0]])
+    assert texts[0] == before and len(rows) > 20
+    assert texts[0].count(b"\n") == len(rows) and eng.render_raw_merged([0]) == texts[0]
+    eng.close()
+
+
+def test_del_three_raw_groups_four_samples():
+    d = del_engine()
+    eng, plan, scheme = d["eng"], d["eng"].plan, d["case"]["scheme"]
+    assert plan.mode == "sparse" and n_samples_of(plan) == 4
+    k = 2048  # the sort's tile: several of them
+    assert len(d["rows"]) > 4 * k
+    on_text_chunks = []
+    n = eng.render_raw_counts(1, on_text=on_text_chunks.append)
+    rows, texts = check_engine(eng, scheme, [[0, 1, 2, 3], [3, 1], [2, 2, 0]])
+    assert rows == d["rows"]
+    assert b"".join(on_text_chunks) == texts[1] and n == texts[1].count(b"\n")
+    assert sum(t.count(b"\n") for t in texts.values()) == len(rows)
+    # the order, said without the renderer: lines ascend by the digit tuple of their own text
+    for t in texts.values():
+        keys = [tuple(rrl.code_of(f.decode()) for f in line.split(b",")[:3]) for line in t.split(b"\n")[:-1]]
+        assert keys == sorted(keys) and len(set(keys)) == len(keys)
+
+
+def test_sort_is_shared_until_the_counts_change():
+    d = del_engine()
+    eng = d["eng"]
+    S = 4
+    eng.render_raw_counts(0)  # (whatever the tests before did: the sort of the current counts exists now)
+    base = eng.raw_render_sorts()
+    assert base >= 1
+    texts = [eng.render_raw_counts(s) for s in range(S)] + [eng.render_raw_merged(range(S))]
+    assert eng.raw_render_sorts() == base and all(texts)
+    # a fresh engine: S + 1 renders move the counter by exactly 1, a submit by 1 more
+    import torch
+    c = d["case"]
+    plan = make_plan(c)
+    seq, _, lens = readgen.to_arrays(c["reads"][:3000], stride=100)
+    dseq = torch.from_numpy(seq.reshape(-1)).cuda()
+    dlens = torch.from_numpy(lens.view(np.int16)).cuda()
+    e2 = _pkg().Engine(plan, device=0)
+    e2.submit_device(dseq.data_ptr(), None, 3000, 100, 100, dlens.data_ptr())
+    assert e2.raw_render_sorts() == 0
+    first = [e2.render_raw_counts(s) for s in range(S)] + [e2.render_raw_merged(range(S))]
+    assert e2.raw_render_sorts() == 1
+    e2.submit_device(dseq.data_ptr(), None, 3000, 100, 100, dlens.data_ptr())
+    second = [e2.render_raw_counts(s) for s in range(S)] + [e2.render_raw_merged(range(S))]
+    assert e2.raw_render_sorts() == 2
+    rows = e2.result_rows()
+    assert second[0] == rrc.expected(plan, c["scheme"], rows, [0], False) and second[0] != first[0]
+    assert second[4] == rrc.expected(plan, c["scheme"], rows, range(S), True)
+    e2.reset()
+    assert e2.render_raw_counts(0) == b"" and e2.raw_render_sorts() == 3
+    e2.close()
+
+
+def test_random_barcode_known_sample_raw_counted():
+    c = rrc.random_raw_case()
+    eng = run(c)
+    plan = eng.plan
+    assert plan.mode == "sparse" and plan.random_barcode and n_samples_of(plan) == 3
+    rows, texts = check_engine(eng, c["scheme"], [[0, 1, 2], [2, 0]])
+    # counts are distinct random barcodes: fewer than the matched reads (dup_frac 0.3), more than the rows
+    total = sum(r[2] for r in rows)
+    k = eng.counters()
+    assert k["duplicates"] > 0 and len(rows) < total == k["matched"]
+    eng.close()
+
+
+def test_imported_keys_at_the_ends_of_the_space():
+    """hand-made keys through bc_engine_import_counts: the smallest and largest key of the space, counts 1 and 2^32-1"""
+    import torch
+    c = rrc.del_raw_case(n=10)
+    plan = make_plan(c)
+    eng = _pkg().Engine(plan, device=0)
+    t_space = 5 ** 24
+    top = 4 * t_space - 1
+    keys = np.array([0, top, 3 * t_space, t_space - 1, 2 * t_space + 5 ** 8], dtype=np.uint64)
+    cnts = np.array([1, 2 ** 32 - 1, 2 ** 32 - 1, 1, 10], dtype=np.uint32)
+    dk = torch.from_numpy(keys.view(np.int64)).cuda()
+    dc = torch.from_numpy(cnts.view(np.int32)).cuda()
+    eng.import_counts(dk.data_ptr(), dc.data_ptr(), len(keys))
+    a, n = b"A" * 8, b"N" * 8
+    assert eng.render_raw_counts(0) == a + b"," + a + b"," + a + b",1\n" + n + b"," + n + b"," + n + b",1\n"
+    assert eng.render_raw_counts(3) == a + b"," + a + b"," + a + b",4294967295\n" + n + b"," + n + b"," + n + b",4294967295\n"
+    assert eng.render_raw_counts(1) == b""
+    assert eng.render_raw_counts(2) == a + b",C" + b"A" * 7 + b"," + a + b",10\n"
+    merged = eng.render_raw_merged([3, 0, 2])
+    assert merged == (a + b"," + a + b"," + a + b",4294967295,1,0\n" + a + b",C" + b"A" * 7 + b"," + a + b",0,0,10\n" +
+                      n + b"," + n + b"," + n + b",4294967295,1,0\n")
+    rows = eng.result_rows()
+    assert eng.render_raw_merged([3, 0, 2]) == rrc.expected(plan, c["scheme"], rows, [3, 0, 2], True)
+    assert eng.raw_render_sorts() == 1
+    eng.close()
+
+
+def test_small_chunks_give_the_same_text(monkeypatch):
+    d = del_engine()
+    eng = d["eng"]
+    whole = [eng.render_raw_counts(2), eng.render_raw_merged([1, 3])]
+    monkeypatch.setenv("BC_RENDER_CHUNK_BYTES", "300")
+    for text, call in zip(whole, (lambda f: eng.render_raw_counts(2, on_text=f), lambda f: eng.render_raw_merged([1, 3], on_text=f))):
+        chunks = []
+        n = call(chunks.append)
+        assert b"".join(chunks) == text and n == text.count(b"\n")
+        assert len(chunks) > 100 and all(0 < len(x) <= 300 and x.endswith(b"\n") for x in chunks)
+
+
+def test_empty_engine():
+    c = rrc.del_raw_case(n=10)
+    eng = _pkg().Engine(make_plan(c), device=0)
+    chunks = []
+    assert eng.render_raw_counts(0, on_text=chunks.append) == 0 and not chunks
+    assert eng.render_raw_merged([0, 1, 2, 3]) == b"" and eng.render_raw_merged([]) == b""
+    eng.close()
+
+
+def test_failing_callback_leaves_the_engine_usable(monkeypatch):
+    pkg = _pkg()
+    d = del_engine()
+    eng = d["eng"]
+    whole = eng.render_raw_counts(0)
+    monkeypatch.setenv("BC_RENDER_CHUNK_BYTES", "4096")
+    seen = []
+
+    def stop(chunk):
+        seen.append(chunk)
+        if len(seen) == 2:
+            raise RuntimeError("stop")
+
+    with pytest.raises((pkg.BarcodeCountError, RuntimeError)) as ex:
+        eng.render_raw_counts(0, on_text=stop)
+    if isinstance(ex.value, pkg.BarcodeCountError):
+        assert ex.value.code == -5
+    assert len(seen) == 2
+    assert eng.render_raw_counts(0) == whole
+    # the C ABI itself: fn != 0 -> BC_ERR_STATE
+    import ctypes as C
+    lib = pkg._lib.load()
+    fail, go_on = pkg._lib.TEXT_FN(lambda t, k, u: 1), pkg._lib.TEXT_FN(lambda t, k, u: 0)
+    n = C.c_uint64(7)
+    rc = lib.bc_engine_render_raw_counts(eng._e, 0, fail, None, C.byref(n))
+    assert rc == -5 and "callback" in pkg._lib.last_error(lib) and n.value == 0
+    assert lib.bc_engine_render_raw_counts(eng._e, 0, None, None, C.byref(n)) == -1      # null callback
+    assert lib.bc_engine_render_raw_counts(eng._e, 4, go_on, None, C.byref(n)) == -1     # sample 4 of 4
+    assert lib.bc_engine_render_raw_merged(eng._e, None, 2, go_on, None, C.byref(n)) == -1  # null list, two columns
+    assert eng.render_raw_counts(0) == whole
+
+
+def test_refusals():
+    pkg = _pkg()
+    import test_gpu_wide_keys as wk
+    dense = run(cases.build_case("del_exact", seed=3, n=300))
+    raw_sample = run(cases.build_case("raw_sample", seed=3, n=300))
+    plan, _, reads = wk._build("barcode_seq_40", 300, 7)
+    wide, _ = wk._run_engine(plan, reads, trace=False)
+    assert dense.plan.mode == "dense" and raw_sample.plan.mode == "sparse" and key_words(wide) > 1
+    for eng, word in ((dense, "bc_engine_render_counts"), (raw_sample, "bc_engine_row_text"), (wide, "bc_engine_row_text")):
+        for call in (lambda: eng.render_raw_counts(0), lambda: eng.render_raw_merged([0])):
+            with pytest.raises(pkg.BarcodeCountError) as ex:
+                call()
+            assert ex.value.code == -2 and word in str(ex.value)
+        assert eng.raw_render_sorts() == 0
+        eng.close()
+
+
+def test_root_renders_the_job_after_finish_all(tmp_path):
+    """2 ranks on one GPU over the message-file transport: the root's text equals the one-engine text of all reads"""
+    d = del_engine()
+    n = len(d["case"]["reads"])
+    cdir = tmp_path / "comm"
+    cdir.mkdir()
+    out = tmp_path / "job.json"
+    env = dict(os.environ, BC_COMM_TIMEOUT_S="120")
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "mp_rank_raw_render.py"), str(r), "2", str(cdir), str(n),
+                               "0", str(out)], env=env, stderr=subprocess.PIPE) for r in range(2)]
+    for r, p in enumerate(procs):
+        _, err = p.communicate(timeout=300)
+        assert p.returncode == 0, (r, err.decode()[-1500:])
+    job = json.load(open(out))
+    eng = d["eng"]
+    for s in range(4):
+        assert job["counts"][s].encode("latin-1") == eng.render_raw_counts(s), s
+    assert job["merged"].encode("latin-1") == eng.render_raw_merged([3, 2, 1, 0])
+    assert job["sorts"] == 1
