@@ -21,14 +21,8 @@
 
 #include "../../include/barcode_count_hip.h"
 #include "bc_kernel.h"
-#include "bc_enrich.h"
-#include "bc_render.h"
-#include "bc_enrich_render.h"
-#include "bc_raw_render.h"
-#include "bc_sort.h"
+#include "bc_engine_impl.h"
 #include "bc_fold.h"
-#include "bc_jit.h"
-#include "bc_plan.hpp"
 #include "bc_synth.h"
 
 extern "C" int bc_internal_table_pack_u8(const void* d_table_u32, const void* d_bits, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64,
@@ -531,167 +525,9 @@ __global__ void synth_kernel(SynthDev S, uint64_t first, uint64_t n, uint8_t* __
 
 using namespace bc;
 
-// A failed HIP call becomes a status + message; running out of device or pinned memory is BC_ERR_NOMEM, not BC_ERR_HIP.
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) {                                                                \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                        \
-      if (_e == hipErrorOutOfMemory) (void)hipGetLastError(); /* not sticky: the engine stays usable */ \
-      return _e == hipErrorOutOfMemory ? BC_ERR_NOMEM : BC_ERR_HIP;                        \
-    }                                                                                      \
-  } while (0)
-
-// Device / pinned scratch that is released on every way out of a function (HIP_TRY returns early).
-struct ScratchGuard {
-  std::vector<void*> dev, pinned;
-  std::vector<hipEvent_t> events;
-  ~ScratchGuard() {
-    for (void* p : dev) (void)hipFree(p);
-    for (void* p : pinned) (void)hipHostFree(p);
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-  }
-  template <typename T>
-  hipError_t dmalloc(T** out, size_t bytes) {
-    void* p = nullptr;
-    const hipError_t rc = hipMalloc(&p, bytes ? bytes : 16);
-    if (rc == hipSuccess) dev.push_back(p);
-    *out = (T*)p;
-    return rc;
-  }
-  template <typename T>
-  hipError_t hmalloc(T** out, size_t bytes) {
-    void* p = nullptr;
-    const hipError_t rc = hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault);
-    if (rc == hipSuccess) pinned.push_back(p);
-    *out = (T*)p;
-    return rc;
-  }
-  hipError_t event(hipEvent_t* out) {
-    const hipError_t rc = hipEventCreateWithFlags(out, hipEventDisableTiming);
-    if (rc == hipSuccess) events.push_back(*out);
-    return rc;
-  }
-};
-
-struct bc_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipStream_t copy_stream = nullptr;
-  HostDevPlan h;
-  DevPlan* d_plan = nullptr;
-  std::vector<void*> allocs;
-  uint32_t* d_table = nullptr;
-  bool own_table = false;
-  uint64_t table_entries = 0;
-  uint32_t* d_bits = nullptr;   // two-level counting: the first-occurrence bit of every tuple (large dense tables)
-  uint64_t n_bit_words = 0;
-  bool bits_dirty = false;      // some bit may be set: fold before anyone reads the table
-  bool table_exposed = false;   // bc_engine_table_ptr has handed the table out: every sync folds, as for a caller's table
-  uint64_t dirty_bytes = 0;     // the dirty-block map behind the bit map (DevPlan::dirty_off): one flag per 64 entries
-  bool table_all_dirty = false; // somebody wrote the table without flagging (a fold, the wave-per-read kernel, a caller
-                                // holding its pointer): the next reset zeroes all of it
-  uint64_t reads_since_fold = 0;  // upper bound on the bits set since then: picks the fold kernel
-  // log-mode counting (bc_fold.h): BC_COUNT_LOG = 0 never | 1 whenever the plan allows it | auto (default): submits of
-  // at least log_min_reads reads (BC_COUNT_LOG_MIN_READS).  Either way the counts are the same.
-  int count_log = 2;
-  uint64_t log_min_reads = 1ull << 24;
-  uint64_t log_chunk = 1ull << 27;   // reads per match launch + fold (BC_COUNT_LOG_CHUNK, a multiple of 64)
-  bool log_hot = false;              // the hot-counter cache in log mode too (BC_COUNT_LOG_HOT=0|1; off: 4.62 vs 4.75 ms
-                                     // for config 3's match kernel -- the fold's LDS atomics take hot tuples in stride)
-  uint64_t log_cap = 0;              // entries allocated in d_log / d_grouped
-  uint32_t* d_log = nullptr;
-  uint32_t* d_grouped = nullptr;
-  uint64_t gz_blocks = 0;            // BGZF blocks inflated on the device for this engine (bc_engine_gz_blocks_inflated)
-  uint64_t log_folds = 0;            // folds run since the engine was created (bc_engine_count_log_folds)
-  uint32_t* d_fold_meta = nullptr;   // [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each
-  // What the last reset owes (settle_owed()): a reset only records it, and whoever touches table, dirty map or bit map
-  // next pays it first, on the engine's stream -- except a log-mode submit, whose match kernel touches none of them:
-  // there the table's part runs on reset_stream beside the match kernel and is joined before the fold
-  // (BC_COUNT_LOG_DEFER_RESET=0|1), and the fold takes the bit map as all zero without anyone writing the zeros first
-  // (bc_fold.h, a fresh fold; BC_COUNT_LOG_FRESH=0|1).  The table's part is only ever owed for a table nobody else can
-  // see (engine-owned, its pointer not handed out): whoever holds a pointer may order work after the reset by the stream.
-  bool owed_table = false;           // the dirty-block reset, or (owed_table_all) table and dirty map zeroed whole
-  bool owed_table_all = false;
-  bool owed_bits = false;            // the bit map zeroed
-  bool defer_reset = true;
-  bool fold_fresh = true;
-  hipStream_t reset_stream = nullptr;  // created with the first deferred reset
-  hipEvent_t reset_fork = nullptr, reset_join = nullptr;
-  unsigned long long* d_counters = nullptr;
-  uint32_t barcode_num = 0;
-  uint32_t n_sets[kMaxGroups] = {0};
-  std::vector<std::vector<std::string>> set_seqs;  // per group: the known sequences in index order
-  bool has_sample_group = false;
-  uint8_t* trace_outcome = nullptr;
-  uint64_t* trace_idx = nullptr;
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  std::vector<float> launch_ms;  // resolved launch times not yet handed out (bc_engine_kernel_ms[_each])
-  // compacted results
-  std::vector<uint64_t> row_idx;
-  std::vector<uint32_t> row_cnt;
-  // host staging (bc_engine_submit_host)
-  static constexpr int kStages = 2;
-  uint8_t* pin[kStages] = {nullptr, nullptr};
-  uint8_t* dev[kStages] = {nullptr, nullptr};
-  hipEvent_t copied[kStages] = {nullptr, nullptr};
-  hipEvent_t consumed[kStages] = {nullptr, nullptr};
-  size_t stage_bytes = 0;
-  uint32_t lds_limit = 0;
-  uint32_t n_cus = 0;
-  JitKernels jit;  // scheme-specialised kernels, one per kernel shape (NW, NWW, lengths, tables, tracing)
-  uint64_t reads_seen = 0;  // reads submitted so far: a cache miss is only worth a compile for a long run
-  int jit_mode = 1;  // BC_JIT = 0: never | 1 (default): cache hit -> at once, else compiled in the background once 2^20
-                     // reads have been seen | force (2): always, compiled synchronously | cached (3): cache hits only
-  std::string last_kernel;
-  bool pipe = true;   // software-pipelined tile fetch (BC_PIPE=0|1)
-  int lhash_mode = 1; // LDS exact-match tables (PlanSetup::lhash_mode)
-  // random-barcode mode: the hash set of (tuple, random barcode) keys
-  unsigned long long* d_slots = nullptr;
-  uint32_t* d_vals = nullptr;  // sparse plans without a random barcode: the count of each key
-  uint64_t n_slots = 0;
-  uint32_t key_words = 1;      // u64 words per key: 1, or the plan's wide keys (bc_long.h)
-  uint32_t* d_ready = nullptr;  // wide keys: a slot's payload has been published
-  std::vector<uint64_t> row_wide;  // compacted rows of a wide-key plan: key_words words per row (row_idx stays empty)
-  uint64_t key_bound = 0;  // upper bound on the keys held: reads submitted / keys imported so far
-  // the wave-per-read kernel's plan (bc_long.h): built when a submit needs it -- reads above 320 bases -- or at
-  // creation when the lane-per-read kernel cannot run the plan at all (long_only)
-  bool long_only = false, long_ready = false;
-  LongHost lh;
-  LongPlan* d_long = nullptr;
-  const bc_plan* src_plan = nullptr;  // (the caller keeps the plan alive for the engine's lifetime)
-  // the label pool of the text renderer (bc_render.h), built at the first render: the IDs of the counted sets
-  bool render_pool_ready = false;
-  uint32_t* d_label_off = nullptr;
-  uint8_t* d_label_bytes = nullptr;
-  uint32_t label_off_start[kMaxGroups] = {0};
-  uint32_t label_max[kMaxGroups] = {0};  // the longest ID of each counted set
-  bool table_materialized = false;  // random-barcode plans: d_table holds the per-tuple distinct counts of the current
-                                    // key set (bc_engine_materialize_table), possibly summed over ranks since
-  // The enrichment renderer (bc_enrich_render.h).  counts_epoch moves whenever what bc_engine_finish would hand out may
-  // have changed (counts_changed()); the folded sums on the device are those of epoch sums_epoch and are served only
-  // while the two agree -- and never for a table somebody else may write (caller-owned, or its pointer handed out).
-  uint64_t counts_epoch = 1, sums_epoch = 0;
-  unsigned long long* d_sums = nullptr;  // S * SUM singles, then S * P doubles
-  uint64_t sums_passes = 0;              // table passes made for them since the engine was created
-  bool canon_ready = false;              // the canonical maps of the label pool have been built
-  uint32_t* d_canon = nullptr;           // canon[off_g + i]; NULL when no set shares an ID
-  // The raw-key renderer (bc_raw_render.h): the map's (key, count) pairs, re-keyed and sorted (bc_sort.h), kept on the
-  // device for the counts of epoch raw_epoch -- the S + 1 renders of one merged run sort once.  Whatever moves
-  // counts_epoch (submits, imports, resets, clear_keys, finish_all) retires them; the next render frees and rebuilds.
-  uint64_t raw_epoch = 0;
-  uint64_t* d_raw_keys = nullptr;
-  uint32_t* d_raw_cnts = nullptr;
-  uint64_t raw_n = 0;
-  uint64_t raw_sorts = 0;                // sorts made since the engine was created (bc_engine_raw_render_sorts)
-  float raw_sort_ms = 0.f;               // export + re-key + sort of the last one, from HIP events
-};
-
 static void counts_changed(bc_engine* e) { ++e->counts_epoch; }
 
-static int upload(bc_engine* e, const void* src, size_t bytes, uint64_t* out) {
+int bc::upload(bc_engine* e, const void* src, size_t bytes, uint64_t* out) {
   void* d = nullptr;
   HIP_TRY(hipMalloc(&d, bytes ? bytes : 16));
   e->allocs.push_back(d);
@@ -986,7 +822,6 @@ static int fold_log(bc_engine* e, uint64_t n, bool fresh) {
   return BC_OK;
 }
 
-static uint32_t grid_for(uint64_t n);
 
 // The two parts of an owed reset (bc_engine::owed_*), enqueued on `st`; each clears its flag once it is enqueued.
 static int settle_table_on(bc_engine* e, hipStream_t st) {
@@ -1235,7 +1070,7 @@ static int launch_long(bc_engine* e, const void* d_seq, const void* d_qual, cons
   return BC_OK;
 }
 
-static uint32_t grid_for(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 256ull * 32); }
+uint32_t bc::grid_for(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 256ull * 32); }
 
 // Random-barcode mode: keeps the hash set at most half full for `more` further keys.  Growing
 // allocates a set of twice the size (or more) and re-inserts the old keys on the device.
@@ -1604,6 +1439,49 @@ int bc_engine_trace(bc_engine* e, void* d_outcome_u8, void* d_index_u64) {
   return BC_OK;
 }
 
+}  // extern "C"
+
+int bc::export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** d_key, uint32_t** d_cnt, uint64_t* n_out) {
+  unsigned long long* keys = e->d_slots;
+  uint32_t* vals = e->d_vals;
+  const uint64_t n_slots = e->n_slots;
+  if (e->h.plan.has_random) {
+    // count of a tuple = number of its distinct random barcodes (output.rs:265-270)
+    unsigned long long* agg_keys = nullptr;
+    uint32_t* agg_vals = nullptr;
+    HIP_TRY(g.dmalloc(&agg_keys, n_slots * 8));
+    HIP_TRY(g.dmalloc(&agg_vals, n_slots * 4));
+    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, agg_keys, n_slots);
+    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
+    hipLaunchKernelGGL(set_to_map_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, n_slots,
+                       e->h.plan.rspace, agg_keys, agg_vals, n_slots - 1);
+    HIP_TRY(hipGetLastError());
+    keys = agg_keys;
+    vals = agg_vals;
+  }
+  unsigned long long* d_n = nullptr;
+  HIP_TRY(g.dmalloc(&d_n, 8));
+  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
+  // upper bound on the rows: the keys held
+  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);
+  HIP_TRY(g.dmalloc(d_key, cap * 8));
+  HIP_TRY(g.dmalloc(d_cnt, cap * 4));
+  hipLaunchKernelGGL(map_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, vals, n_slots, d_n, *d_key,
+                     *d_cnt);
+  HIP_TRY(hipGetLastError());
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (n > cap) {  // (cannot happen: key_bound counts every insert)
+    set_error(std::string(who) + ": the key map holds more keys than its bound");
+    return BC_ERR_STATE;
+  }
+  *n_out = n;
+  return BC_OK;
+}
+
+extern "C" {
+
 // rows of a sparse plan: (tuple key, count) pairs straight out of the hash map
 static int finish_sparse(bc_engine* e, uint64_t* n_rows) {
   const DevPlan& P = e->h.plan;
@@ -1613,11 +1491,11 @@ static int finish_sparse(bc_engine* e, uint64_t* n_rows) {
   e->row_wide.clear();
   if (!e->d_slots) return BC_OK;
   ScratchGuard g;
-  unsigned long long* keys = e->d_slots;
-  uint32_t* vals = e->d_vals;
-  uint64_t n_slots = e->n_slots;
   if (e->key_words > 1) {
-    // wide keys (bc_long.h): the same two steps on slots of key_words words
+    // wide keys (bc_long.h): the two steps of export_pairs on slots of key_words words
+    unsigned long long* keys = e->d_slots;
+    uint32_t* vals = e->d_vals;
+    const uint64_t n_slots = e->n_slots;
     const uint32_t W = e->key_words;
     const uint32_t* ready = e->d_ready;
     if (P.has_random) {
@@ -1669,35 +1547,11 @@ static int finish_sparse(bc_engine* e, uint64_t* n_rows) {
     if (n_rows) *n_rows = n;
     return BC_OK;
   }
-  if (P.has_random) {
-    // count of a tuple = number of its distinct random barcodes (output.rs:265-270)
-    unsigned long long* agg_keys = nullptr;
-    uint32_t* agg_vals = nullptr;
-    HIP_TRY(g.dmalloc(&agg_keys, n_slots * 8));
-    HIP_TRY(g.dmalloc(&agg_vals, n_slots * 4));
-    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, agg_keys, n_slots);
-    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
-    hipLaunchKernelGGL(set_to_map_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, n_slots, P.rspace,
-                       agg_keys, agg_vals, n_slots - 1);
-    HIP_TRY(hipGetLastError());
-    keys = agg_keys;
-    vals = agg_vals;
-  }
-  unsigned long long* d_n = nullptr;
   uint64_t* d_key = nullptr;
   uint32_t* d_cnt = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  // upper bound on the rows: the keys held
-  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);
-  HIP_TRY(g.dmalloc(&d_key, cap * 8));
-  HIP_TRY(g.dmalloc(&d_cnt, cap * 4));
-  hipLaunchKernelGGL(map_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, vals, n_slots, d_n, d_key,
-                     d_cnt);
-  HIP_TRY(hipGetLastError());
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  uint64_t n = 0;
+  const int rc = export_pairs(e, "bc_engine_finish", g, &d_key, &d_cnt, &n);
+  if (rc != BC_OK) return rc;
   try {
     e->row_idx.resize(n);
     e->row_cnt.resize(n);
@@ -1828,15 +1682,16 @@ int bc_engine_nonzero_entries(bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
-// What every reader of a dense plan's counts does first (bc_engine_finish, bc_engine_enrich): wait for the submits, and
-// for a random-barcode plan turn the key set into per-tuple counts unless that has been done for the current keys.
-// Afterwards entry i counts table[i] + bit i of the bit map (when e->bits_dirty: two-level counting, not folded).
-static int dense_counts_ready(bc_engine* e) {
+}  // extern "C"
+
+int bc::dense_counts_ready(bc_engine* e) {
   int rc = bc_engine_sync(e);
   if (rc) return rc;
   if (e->h.plan.has_random && !e->table_materialized) return bc_engine_materialize_table(e);
   return BC_OK;
 }
+
+extern "C" {
 
 // rows of either kind of plan, chunk by chunk (bc_engine_finish_stream); for sparse plans the chunks are cut from the
 // exported map
@@ -1942,8 +1797,9 @@ int bc_engine_decode_index(const bc_engine* e, uint64_t dense_index, uint32_t* s
   return BC_OK;
 }
 
-// The shape of a dense plan's enrichment (bc_engine_enrich); false + set_error() for plans that have none.
-static bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples) {
+}  // extern "C"
+
+bool bc::enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples) {
   const DevPlan& P = e->h.plan;
   if (P.sparse) {
     set_error(std::string(who) + ": the plan keeps raw captures, whose keys are sequences, not indices: enrich its rows "
@@ -1973,6 +1829,8 @@ static bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, u
   *n_samples = sh->inner ? e->table_entries / sh->inner : 0;
   return true;
 }
+
+extern "C" {
 
 int bc_engine_enrich_entries(const bc_engine* e, uint64_t* single_entries, uint64_t* double_entries) {
   EnrichShape sh;
@@ -2009,644 +1867,6 @@ int bc_engine_enrich(bc_engine* e, uint64_t* single_counts, uint64_t* double_cou
   if (n_double) HIP_TRY(hipMemcpyAsync(double_counts, d_double, n_double * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return BC_OK;
-}
-
-// ---- counts as text (bc_render.h / bc_render.hip) ----
-
-// The IDs of the counted sets on the device, once per engine: per group N_g + 1 offsets, and the bytes back to back.
-static int ensure_render_pool(bc_engine* e, const char* who) {
-  if (e->render_pool_ready) return BC_OK;
-  const uint32_t G = e->barcode_num;
-  std::vector<uint32_t> off;
-  std::string bytes;
-  try {
-    for (uint32_t g = 0; g < G; ++g) {
-      e->label_off_start[g] = (uint32_t)off.size();
-      e->label_max[g] = 0;
-      const uint32_t n = bc_plan_n_counted(e->src_plan, g);
-      for (uint32_t i = 0; i < n; ++i) {
-        const char* id = bc_plan_counted_id(e->src_plan, g, i);
-        const size_t len = id ? strlen(id) : 0;
-        if (bytes.size() + len > 0xFFFFFFF0ull || off.size() > 0xFFFFFFF0ull) {
-          set_error(std::string(who) + ": the IDs of the counted barcodes pass 4 GB");
-          return BC_ERR_UNSUPPORTED;
-        }
-        off.push_back((uint32_t)bytes.size());
-        if (len) bytes.append(id, len);
-        e->label_max[g] = std::max<uint32_t>(e->label_max[g], (uint32_t)len);
-      }
-      off.push_back((uint32_t)bytes.size());
-    }
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return BC_ERR_NOMEM;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  // both parts in one allocation (offsets first: the bytes need no alignment), so a failure leaves nothing behind
-  const size_t off_bytes = off.size() * 4;
-  std::string image;
-  try {
-    image.assign((const char*)off.data(), off_bytes);
-    image += bytes;
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return BC_ERR_NOMEM;
-  }
-  void* d_pool = nullptr;
-  HIP_TRY(hipMalloc(&d_pool, image.size() ? image.size() : 16));
-  if (!image.empty()) {
-    const hipError_t hrc = hipMemcpy(d_pool, image.data(), image.size(), hipMemcpyHostToDevice);
-    if (hrc != hipSuccess) {
-      (void)hipFree(d_pool);
-      HIP_TRY(hrc);
-    }
-  }
-  try {
-    e->allocs.push_back(d_pool);
-  } catch (const std::bad_alloc&) {
-    (void)hipFree(d_pool);
-    set_error(std::string(who) + ": out of host memory");
-    return BC_ERR_NOMEM;
-  }
-  e->d_label_off = (uint32_t*)d_pool;
-  e->d_label_bytes = (uint8_t*)d_pool + off_bytes;
-  e->render_pool_ready = true;
-  return BC_OK;
-}
-
-}  // extern "C"  (overloads and a template: C++ linkage)
-
-// The three passes of a text render (bc_text_kernels.h) for either view, enqueued on `st`.
-static hipError_t text_sizes(const bc::RenderView& v, uint64_t nb, uint32_t* d_rows, unsigned long long* d_bytes, hipStream_t st) {
-  return bc_render_sizes_launch(v, nb, d_rows, d_bytes, st);
-}
-static hipError_t text_sizes(const bc::EnrichRenderView& v, uint64_t nb, uint32_t* d_rows, unsigned long long* d_bytes,
-                             hipStream_t st) {
-  return bc_enrich_render_sizes_launch(v, nb, d_rows, d_bytes, st);
-}
-static hipError_t text_lens(const bc::RenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t st) {
-  return bc_render_lens_launch(v, lo, n, d_len, st);
-}
-static hipError_t text_lens(const bc::EnrichRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t st) {
-  return bc_enrich_render_lens_launch(v, lo, n, d_len, st);
-}
-static hipError_t text_write(const bc::RenderView& v, uint64_t b0, uint64_t nb, uint64_t lo, uint64_t hi, const uint32_t* d_rows,
-                             const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out, uint64_t out_cap, hipStream_t st) {
-  return bc_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
-}
-static hipError_t text_write(const bc::EnrichRenderView& v, uint64_t b0, uint64_t nb, uint64_t lo, uint64_t hi,
-                             const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
-                             uint64_t out_cap, hipStream_t st) {
-  return bc_enrich_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
-}
-
-static hipError_t text_sizes(const bc::RawRenderView& v, uint64_t nb, uint32_t* d_rows, unsigned long long* d_bytes, hipStream_t st) {
-  return bc_raw_render_sizes_launch(v, nb, d_rows, d_bytes, st);
-}
-static hipError_t text_lens(const bc::RawRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t st) {
-  return bc_raw_render_lens_launch(v, lo, n, d_len, st);
-}
-static hipError_t text_write(const bc::RawRenderView& v, uint64_t b0, uint64_t nb, uint64_t lo, uint64_t hi,
-                             const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
-                             uint64_t out_cap, hipStream_t st) {
-  return bc_raw_render_write_launch(v, b0, nb, lo, hi, d_rows, d_prefix, sub, d_out, out_cap, st);
-}
-
-// The lines of the keys [0, n_keys) that have one, in ascending key order, handed to `fn` in chunks that end with a
-// line.  Pass 1 sizes every block of the key space, the host scans the sizes and cuts the space into ranges whose text
-// fits one staging buffer, pass 2 writes range after range into one of two buffers (device + pinned) while the host hands
-// on the range before.  A block whose text passes the buffer is cut between its lines from their lengths.  Device
-// memory: 2 x buffer + 12 bytes per block of 1024 keys.  max_line: no line is longer.
-template <class View>
-static int stream_text(bc_engine* e, const char* who, const View& v, uint64_t max_line, bc_text_fn fn, void* user,
-                       uint64_t* n_rows) {
-  const uint64_t n_keys = bc::text_keys(v);
-  uint64_t cap = 64ull << 20;
-  if (const char* ev = getenv("BC_RENDER_CHUNK_BYTES")) {  // (a value that does not parse, or 0, leaves the default)
-    char* end = nullptr;
-    const unsigned long long x = strtoull(ev, &end, 0);
-    if (end != ev && *end == '\0' && x > 0) cap = x;
-  }
-  cap = std::max(cap, max_line);  // never smaller than the longest possible line: every line fits some chunk
-
-  ScratchGuard g;
-  const uint64_t n_blocks = (n_keys + kRenderBlock - 1) / kRenderBlock;
-  uint32_t* d_rows = nullptr;
-  unsigned long long* d_bytes = nullptr;
-  HIP_TRY(g.dmalloc(&d_rows, n_blocks * 4));
-  HIP_TRY(g.dmalloc(&d_bytes, (n_blocks + 1) * 8));
-  HIP_TRY(hipMemsetAsync(d_rows, 0, n_blocks * 4, e->stream));
-  HIP_TRY(hipMemsetAsync(d_bytes, 0, (n_blocks + 1) * 8, e->stream));
-  HIP_TRY(text_sizes(v, n_blocks, d_rows, d_bytes, e->stream));
-  std::vector<uint32_t> rows;
-  std::vector<unsigned long long> prefix;
-  try {
-    rows.resize(n_blocks);
-    prefix.resize(n_blocks + 1);
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return BC_ERR_NOMEM;
-  }
-  HIP_TRY(hipMemcpyAsync(rows.data(), d_rows, n_blocks * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(prefix.data(), d_bytes, n_blocks * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  uint64_t total_rows = 0, total_bytes = 0;
-  for (uint64_t b = 0; b < n_blocks; ++b) {  // sizes -> exclusive scan, in place
-    const uint64_t x = prefix[b];
-    prefix[b] = total_bytes;
-    total_bytes += x;
-    total_rows += rows[b];
-  }
-  prefix[n_blocks] = total_bytes;
-  if (total_rows == 0) return BC_OK;
-  HIP_TRY(hipMemcpyAsync(d_bytes, prefix.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, e->stream));
-
-  const uint64_t slot = std::min(cap, total_bytes);
-  const size_t slot_alloc = (size_t)((slot + 3) & ~3ull);
-  uint8_t* d_text[2] = {nullptr, nullptr};
-  uint8_t* h_text[2] = {nullptr, nullptr};
-  hipEvent_t landed[2] = {nullptr, nullptr};
-  for (int k = 0; k < 2; ++k) {
-    HIP_TRY(g.dmalloc(&d_text[k], slot_alloc));
-    HIP_TRY(g.hmalloc(&h_text[k], slot_alloc));
-    HIP_TRY(g.event(&landed[k]));
-    if (total_bytes <= cap) break;  // one range: one slot
-  }
-  uint32_t *d_len = nullptr, *h_len = nullptr;  // a block's line lengths, when one has to be cut inside
-  uint64_t pending[2] = {0, 0};
-  auto consume = [&](int k) -> int {
-    HIP_TRY(hipEventSynchronize(landed[k]));
-    if (pending[k] && fn((const char*)h_text[k], (size_t)pending[k], user) != 0) {
-      set_error(std::string(who) + ": stopped by the callback");
-      return BC_ERR_STATE;
-    }
-    return BC_OK;
-  };
-  int64_t seg = 0;
-  // one range: the lines of tuples [lo, hi) inside blocks [b0, b1), `bytes` of text that starts at scan position `sub`
-  auto emit = [&](uint64_t b0, uint64_t b1, uint64_t lo, uint64_t hi, uint64_t sub, uint64_t bytes) -> int {
-    const int k = (int)(seg & 1);
-    if (bytes) {
-      HIP_TRY(text_write(v, b0, b1 - b0, lo, hi, d_rows, d_bytes, sub, d_text[k], slot, e->stream));
-      HIP_TRY(hipMemcpyAsync(h_text[k], d_text[k], bytes, hipMemcpyDeviceToHost, e->stream));
-    }
-    pending[k] = bytes;
-    HIP_TRY(hipEventRecord(landed[k], e->stream));
-    int r2 = BC_OK;
-    if (seg >= 1) r2 = consume(k ^ 1);
-    ++seg;
-    return r2;
-  };
-  auto run = [&]() -> int {
-    uint64_t b0 = 0;
-    while (b0 < n_blocks) {
-      uint64_t b1 = b0;
-      while (b1 < n_blocks && prefix[b1 + 1] - prefix[b0] <= slot) ++b1;
-      int r2;
-      if (b1 > b0) {
-        if (prefix[b1] == prefix[b0]) {  // (nothing but empty blocks)
-          b0 = b1;
-          continue;
-        }
-        r2 = emit(b0, b1, b0 * kRenderBlock, std::min<uint64_t>(n_keys, b1 * kRenderBlock), prefix[b0], prefix[b1] - prefix[b0]);
-        if (r2 != BC_OK) return r2;
-        b0 = b1;
-        continue;
-      }
-      // block b0 alone passes the buffer: cut it between its lines
-      if (!d_len) {
-        HIP_TRY(g.dmalloc(&d_len, kRenderBlock * 4));
-        HIP_TRY(g.hmalloc(&h_len, kRenderBlock * 4));
-      }
-      const uint64_t t0 = b0 * kRenderBlock;
-      const uint32_t n = (uint32_t)std::min<uint64_t>(kRenderBlock, n_keys - t0);
-      HIP_TRY(text_lens(v, t0, n, d_len, e->stream));
-      HIP_TRY(hipMemcpyAsync(h_len, d_len, n * 4, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-      uint32_t len[kRenderBlock];  // (a copy: h_len is reused by a later block while ranges are in flight)
-      memcpy(len, h_len, n * 4);
-      uint32_t i = 0;
-      while (i < n) {
-        uint64_t bytes = 0;
-        uint32_t j = i;
-        while (j < n && bytes + len[j] <= slot) bytes += len[j++];  // (a line always fits: slot >= max_line)
-        if (bytes && (r2 = emit(b0, b0 + 1, t0 + i, t0 + j, prefix[b0], bytes)) != BC_OK) return r2;
-        i = j;
-      }
-      ++b0;
-    }
-    return seg ? consume((int)((seg - 1) & 1)) : BC_OK;
-  };
-  const int rc = run();
-  (void)hipStreamSynchronize(e->stream);  // nothing of ours may still be writing the staging buffers when they go
-  if (rc == BC_OK && n_rows) *n_rows = total_rows;
-  return rc;
-}
-
-extern "C" {
-
-// The lines of the tuples for which some listed sample counts, in ascending tuple order (stream_text).
-static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, void* user,
-                       uint64_t* n_rows) {
-  if (n_rows) *n_rows = 0;
-  const DevPlan& P = e->h.plan;
-  if (P.sparse) {
-    set_error(std::string(who) + ": the plan keeps raw captures, whose rows are sequences, not indices: write them from "
-              "bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (!fn || (n_cols && !cols)) {
-    set_error(std::string(who) + ": null callback or sample list");
-    return BC_ERR_INVALID;
-  }
-  static_assert(bc::kRenderMaxG >= kMaxGroups, "a plan's counted barcodes fit the view");
-  bc::RenderView v;
-  memset(&v, 0, sizeof v);
-  v.G = e->barcode_num;
-  v.T = 1;
-  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    v.n[g] = P.groups[g0 + g].n_refs;
-    v.T *= v.n[g];
-  }
-  const uint64_t S = v.T ? e->table_entries / v.T : 0;
-  for (uint32_t c = 0; c < n_cols; ++c)
-    if (cols[c] >= S) {
-      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
-      return BC_ERR_INVALID;
-    }
-  int rc = dense_counts_ready(e);
-  if (rc) return rc;
-  if (n_cols == 0 || v.T == 0 || e->table_entries == 0) return BC_OK;
-  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    if (bc_plan_n_counted(e->src_plan, g) != v.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
-      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-      return BC_ERR_STATE;
-    }
-    v.off_start[g] = e->label_off_start[g];
-    max_line += e->label_max[g];
-  }
-  if (max_line > bc::kRenderMaxLine) {
-    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
-              std::to_string(bc::kRenderMaxLine));
-    return BC_ERR_UNSUPPORTED;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
-  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
-  v.table = e->d_table;
-  v.bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
-  v.cols = d_cols;
-  v.n_cols = n_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
-}
-
-int bc_engine_render_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
-  return render_text(e, "bc_engine_render_counts", &sample_idx, 1, fn, user, n_rows);
-}
-
-int bc_engine_render_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
-                            uint64_t* n_rows) {
-  return render_text(e, "bc_engine_render_merged", sample_idx, n_samples, fn, user, n_rows);
-}
-
-// ---- counts of a raw-key plan as text (bc_raw_render.h / bc_raw_render.hip, bc_sort.h) ----
-
-static void raw_sorted_drop(bc_engine* e) {
-  if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
-  if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
-  e->d_raw_keys = nullptr;
-  e->d_raw_cnts = nullptr;
-  e->raw_n = 0;
-  e->raw_epoch = 0;
-}
-
-// The pairs of the current counts, sorted into the order of the files, in e->d_raw_keys / d_raw_cnts (raw_n of them):
-// served as they are while the counts epoch stands, else exported from the map (a random-barcode plan's key set first
-// aggregated into per-tuple distinct counts, as finish_sparse does), re-keyed and sorted.  Device memory while it runs:
-// the map's export bound x 12 bytes (kept), the same again for the sort's other buffers and n / 2 bytes of histograms.
-static int ensure_raw_sorted(bc_engine* e, uint64_t t_space, uint32_t S) {
-  if (e->raw_epoch == e->counts_epoch) return BC_OK;
-  const DevPlan& P = e->h.plan;
-  raw_sorted_drop(e);
-  if (!e->d_slots) {  // nothing was ever submitted or imported
-    e->raw_epoch = e->counts_epoch;
-    return BC_OK;
-  }
-  ScratchGuard g;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIP_TRY(hipEventCreate(&ev0));
-  g.events.push_back(ev0);
-  HIP_TRY(hipEventCreate(&ev1));
-  g.events.push_back(ev1);
-  HIP_TRY(hipEventRecord(ev0, e->stream));
-  unsigned long long* keys = e->d_slots;
-  uint32_t* vals = e->d_vals;
-  const uint64_t n_slots = e->n_slots;
-  if (P.has_random) {
-    // count of a tuple = number of its distinct random barcodes (output.rs:265-270)
-    unsigned long long* agg_keys = nullptr;
-    uint32_t* agg_vals = nullptr;
-    HIP_TRY(g.dmalloc(&agg_keys, n_slots * 8));
-    HIP_TRY(g.dmalloc(&agg_vals, n_slots * 4));
-    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, agg_keys, n_slots);
-    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
-    hipLaunchKernelGGL(set_to_map_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, n_slots, P.rspace,
-                       agg_keys, agg_vals, n_slots - 1);
-    HIP_TRY(hipGetLastError());
-    keys = agg_keys;
-    vals = agg_vals;
-  }
-  unsigned long long* d_n = nullptr;
-  uint64_t* d_key = nullptr;
-  uint32_t* d_cnt = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);  // upper bound on the rows: the keys held
-  HIP_TRY(g.dmalloc(&d_key, cap * 8));
-  HIP_TRY(g.dmalloc(&d_cnt, cap * 4));
-  hipLaunchKernelGGL(map_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, vals, n_slots, d_n, d_key, d_cnt);
-  HIP_TRY(hipGetLastError());
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (n > cap) {  // (cannot happen: key_bound counts every insert)
-    set_error("raw render: the key map holds more keys than its bound");
-    return BC_ERR_STATE;
-  }
-  if (n) {
-    uint64_t* d_key2 = nullptr;
-    uint32_t *d_cnt2 = nullptr, *d_scratch = nullptr;
-    HIP_TRY(g.dmalloc(&d_key2, n * 8));
-    HIP_TRY(g.dmalloc(&d_cnt2, n * 4));
-    HIP_TRY(g.dmalloc(&d_scratch, bc::sort_scratch_words(n) * 4));
-    HIP_TRY(bc_raw_rekey_launch(d_key, n, t_space, S, e->stream));
-    uint32_t key_bits = 1;  // the bit length of the largest key of the space (the re-keyed digits have the same radices)
-    while (key_bits < 64 && ((e->h.table_entries - 1) >> key_bits) != 0) ++key_bits;
-    const hipError_t src = bc::sort_pairs_launch(e->stream, d_key, d_cnt, d_key2, d_cnt2, n, key_bits, d_scratch);
-    if (src == hipErrorInvalidValue) {
-      set_error("raw render: " + std::to_string(n) + " rows pass what one sort takes (2^32); write them from bc_engine_row_text on the host");
-      return BC_ERR_UNSUPPORTED;
-    }
-    HIP_TRY(src);
-  }
-  HIP_TRY(hipEventRecord(ev1, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipEventElapsedTime(&e->raw_sort_ms, ev0, ev1);
-  for (void* keep : {(void*)d_key, (void*)d_cnt}) g.dev.erase(std::find(g.dev.begin(), g.dev.end(), keep));
-  e->d_raw_keys = d_key;
-  e->d_raw_cnts = d_cnt;
-  e->raw_n = n;
-  e->raw_epoch = e->counts_epoch;
-  ++e->raw_sorts;
-  return BC_OK;
-}
-
-static int render_raw(bc_engine* e, const char* who, bool merged, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
-                      void* user, uint64_t* n_rows) {
-  if (n_rows) *n_rows = 0;
-  const DevPlan& P = e->h.plan;
-  if (!P.sparse) {
-    set_error(std::string(who) + ": the plan has a dense table: its files come from bc_engine_render_counts / "
-              "bc_engine_render_merged");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->key_words > 1) {
-    set_error(std::string(who) + ": the plan's keys are " + std::to_string(e->key_words) +
-              " words wide; write its rows from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
-    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: write the rows "
-              "from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (!fn || (n_cols && !cols)) {
-    set_error(std::string(who) + ": null callback or sample list");
-    return BC_ERR_INVALID;
-  }
-  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
-  const uint32_t S = g0 ? P.groups[0].n_refs : 1u;
-  const uint64_t t_space = g0 ? P.groups[0].table_stride : e->h.table_entries;
-  for (uint32_t c = 0; c < n_cols; ++c)
-    if (cols[c] >= S) {
-      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
-      return BC_ERR_INVALID;
-    }
-  bc::RawRenderView v;
-  memset(&v, 0, sizeof v);
-  v.G = e->barcode_num;
-  v.S = S;
-  v.merged = merged ? 1u : 0u;
-  v.sample = n_cols ? cols[0] : 0u;
-  v.n_cols = n_cols;
-  if (v.G > (uint32_t)bc::kRenderMaxG || g0 + v.G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
-    set_error(std::string(who) + ": the plan's groups do not fit the view");
-    return BC_ERR_STATE;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = bc_engine_sync(e);  // the submits, as bc_engine_finish waits for them
-  if (rc) return rc;
-  if ((rc = ensure_raw_sorted(e, t_space, S)) != BC_OK) return rc;
-  if (n_cols == 0 || e->raw_n == 0) return BC_OK;
-  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    const DevGroup& G = P.groups[g0 + g];
-    if (G.mode == kSetNone) {
-      v.raw_len[g] = G.len;
-      v.radix[g] = 1;
-      for (uint32_t k = 0; k < G.len; ++k) v.radix[g] *= 5;
-      max_line += G.len;
-    } else {
-      if (bc_plan_n_counted(e->src_plan, g) != G.n_refs) {  // (cannot happen: the key's digits are the plan's sets)
-        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-        return BC_ERR_STATE;
-      }
-      v.radix[g] = G.n_refs;
-      v.off_start[g] = e->label_off_start[g];
-      max_line += e->label_max[g];
-    }
-  }
-  if (max_line > bc::kRenderMaxLine) {
-    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
-              std::to_string(bc::kRenderMaxLine));
-    return BC_ERR_UNSUPPORTED;
-  }
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
-  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
-  v.keys = e->d_raw_keys;
-  v.cnts = e->d_raw_cnts;
-  v.n = e->raw_n;
-  v.cols = d_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
-}
-
-int bc_engine_render_raw_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
-  return render_raw(e, "bc_engine_render_raw_counts", false, &sample_idx, 1, fn, user, n_rows);
-}
-
-int bc_engine_render_raw_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
-                                uint64_t* n_rows) {
-  return render_raw(e, "bc_engine_render_raw_merged", true, sample_idx, n_samples, fn, user, n_rows);
-}
-
-int bc_engine_raw_render_sorts(const bc_engine* e, uint64_t* n) {
-  *n = e->raw_sorts;
-  return BC_OK;
-}
-
-int bc_engine_raw_render_sort_ms(const bc_engine* e, double* ms) {
-  *ms = (double)e->raw_sort_ms;
-  return BC_OK;
-}
-
-// ---- Single / Double enrichment as text (bc_enrich_render.h / bc_enrich_render.hip) ----
-
-// For every counted set, which entries share an ID: canon[off_g + i] = the smallest index of set g whose ID equals i's.
-// Built once per engine, next to the label pool; uploaded only when some set does share an ID.
-static int ensure_canon(bc_engine* e, const char* who) {
-  if (e->canon_ready) return BC_OK;
-  std::vector<uint32_t> canon;
-  bool shared = false;
-  try {
-    for (uint32_t g = 0; g < e->barcode_num; ++g) {
-      std::unordered_map<std::string, uint32_t> first;
-      const uint32_t n = bc_plan_n_counted(e->src_plan, g);
-      for (uint32_t i = 0; i < n; ++i) {
-        const char* id = bc_plan_counted_id(e->src_plan, g, i);
-        const uint32_t c = first.emplace(id ? id : "", i).first->second;
-        shared = shared || c != i;
-        canon.push_back(c);
-      }
-    }
-  } catch (const std::bad_alloc&) {
-    set_error(std::string(who) + ": out of host memory");
-    return BC_ERR_NOMEM;
-  }
-  if (shared) {
-    uint64_t d = 0;
-    const int rc = upload(e, canon.data(), canon.size() * 4, &d);
-    if (rc != BC_OK) return rc;
-    e->d_canon = (uint32_t*)(uintptr_t)d;
-  }
-  e->canon_ready = true;
-  return BC_OK;
-}
-
-// the view of one kind over the engine's sums (cols / n_cols left to the caller)
-static bc::EnrichRenderView enrich_view(const bc_engine* e, const EnrichShape& sh, uint64_t S, uint32_t kind) {
-  bc::EnrichRenderView v;
-  memset(&v, 0, sizeof v);
-  v.kind = kind;
-  v.G = sh.G;
-  v.K = kind == bc::kEnrichSingle ? sh.sum_n : sh.pairs;
-  v.sums = e->d_sums + (kind == bc::kEnrichSingle ? 0 : S * sh.sum_n);
-  v.canon = e->d_canon;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-  for (uint32_t g = 0; g < sh.G; ++g) {
-    v.n[g] = sh.n[g];
-    v.off_start[g] = e->label_off_start[g];
-  }
-  return v;
-}
-
-// The folded sums of the counts as they stand, on the device: computed by one pass over the table (bc_enrich_launch) and
-// the fold, then kept until the counts may have changed (counts_epoch).
-static int ensure_sums(bc_engine* e, const EnrichShape& sh, uint64_t S) {
-  const bool keep = e->own_table && !e->table_exposed;  // (nobody else can write the table between two renders)
-  if (e->d_sums && keep && e->sums_epoch == e->counts_epoch) return BC_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  const uint64_t n_single = S * sh.sum_n, n_double = S * sh.pairs;
-  e->sums_epoch = 0;
-  if (!e->d_sums) HIP_TRY(hipMalloc((void**)&e->d_sums, (size_t)(n_single + n_double) * 8));
-  HIP_TRY(hipMemsetAsync(e->d_sums, 0, (size_t)(n_single + n_double) * 8, e->stream));
-  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, e->d_sums,
-                           n_double ? e->d_sums + n_single : nullptr, e->stream));
-  if (e->d_canon) {
-    HIP_TRY(bc_enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichSingle), S, e->stream));
-    if (n_double) HIP_TRY(bc_enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichDouble), S, e->stream));
-  }
-  ++e->sums_passes;
-  if (keep) e->sums_epoch = e->counts_epoch;
-  return BC_OK;
-}
-
-static int render_enriched(bc_engine* e, const char* who, int kind, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
-                           void* user, uint64_t* n_rows) {
-  if (n_rows) *n_rows = 0;
-  EnrichShape sh;
-  uint64_t S = 0;
-  if (!enrich_shape(e, who, &sh, &S)) return BC_ERR_UNSUPPORTED;
-  if (kind != BC_ENRICH_SINGLE && kind != BC_ENRICH_DOUBLE) {
-    set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
-    return BC_ERR_INVALID;
-  }
-  if (!fn || (n_cols && !cols)) {
-    set_error(std::string(who) + ": null callback or sample list");
-    return BC_ERR_INVALID;
-  }
-  for (uint32_t c = 0; c < n_cols; ++c)
-    if (cols[c] >= S) {
-      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
-      return BC_ERR_INVALID;
-    }
-  int rc = dense_counts_ready(e);
-  if (rc) return rc;
-  const uint64_t K = kind == BC_ENRICH_SINGLE ? sh.sum_n : sh.pairs;  // (no pairs below three counted barcodes)
-  if (n_cols == 0 || K == 0 || e->table_entries == 0) return BC_OK;
-  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  if ((rc = ensure_canon(e, who)) != BC_OK) return rc;
-  uint32_t longest[2] = {0, 0};  // the two longest IDs of different sets
-  for (uint32_t g = 0; g < sh.G; ++g) {
-    if (bc_plan_n_counted(e->src_plan, g) != sh.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
-      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-      return BC_ERR_STATE;
-    }
-    const uint32_t m = e->label_max[g];
-    if (m > longest[0]) {
-      longest[1] = longest[0];
-      longest[0] = m;
-    } else if (m > longest[1]) {
-      longest[1] = m;
-    }
-  }
-  const uint64_t max_line = 1 + (sh.G - 1) + 21ull * n_cols + longest[0] + (kind == BC_ENRICH_DOUBLE ? longest[1] : 0u);
-  if (max_line > bc::kRenderMaxLine) {
-    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
-              std::to_string(bc::kRenderMaxLine));
-    return BC_ERR_UNSUPPORTED;
-  }
-  if ((rc = ensure_sums(e, sh, S)) != BC_OK) return rc;
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
-  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
-  bc::EnrichRenderView v = enrich_view(e, sh, S, (uint32_t)kind);
-  v.cols = d_cols;
-  v.n_cols = n_cols;
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
-}
-
-int bc_engine_render_enriched(bc_engine* e, int kind, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
-  return render_enriched(e, "bc_engine_render_enriched", kind, &sample_idx, 1, fn, user, n_rows);
-}
-
-int bc_engine_render_enriched_merged(bc_engine* e, int kind, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn,
-                                     void* user, uint64_t* n_rows) {
-  return render_enriched(e, "bc_engine_render_enriched_merged", kind, sample_idx, n_samples, fn, user, n_rows);
 }
 
 // Random-barcode plans with a dense table: the count of a tuple is the number of distinct random barcodes seen with it
@@ -2998,10 +2218,6 @@ int bc_engine_count_log_folds(const bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
-int bc_engine_enrich_render_passes(const bc_engine* e, uint64_t* n) {
-  *n = e->sums_passes;
-  return BC_OK;
-}
 int bc_engine_gz_blocks_inflated(const bc_engine* e, uint64_t* n) {
   *n = e->gz_blocks;
   return BC_OK;

@@ -1,0 +1,196 @@
+// bc_engine_impl.h -- what the engine's translation units (bc_engine.hip, bc_text.hip) share: struct bc_engine, the
+// HIP_TRY / ScratchGuard pair every function of the C ABI is written with, and the few engine functions the text
+// renderers call.  Internal: no other file includes it.
+#ifndef BC_ENGINE_IMPL_H
+#define BC_ENGINE_IMPL_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/barcode_count_hip.h"
+#include "bc_enrich.h"
+#include "bc_jit.h"
+#include "bc_plan.hpp"
+
+// A failed HIP call becomes a status + message; running out of device or pinned memory is BC_ERR_NOMEM, not BC_ERR_HIP.
+#define HIP_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) {                                                                \
+      bc::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
+      if (_e == hipErrorOutOfMemory) (void)hipGetLastError(); /* not sticky: the engine stays usable */ \
+      return _e == hipErrorOutOfMemory ? BC_ERR_NOMEM : BC_ERR_HIP;                        \
+    }                                                                                      \
+  } while (0)
+
+// Device / pinned scratch that is released on every way out of a function (HIP_TRY returns early).
+struct ScratchGuard {
+  std::vector<void*> dev, pinned;
+  std::vector<hipEvent_t> events;
+  ~ScratchGuard() {
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : pinned) (void)hipHostFree(p);
+    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+  }
+  template <typename T>
+  hipError_t dmalloc(T** out, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t rc = hipMalloc(&p, bytes ? bytes : 16);
+    if (rc == hipSuccess) dev.push_back(p);
+    *out = (T*)p;
+    return rc;
+  }
+  template <typename T>
+  hipError_t hmalloc(T** out, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t rc = hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault);
+    if (rc == hipSuccess) pinned.push_back(p);
+    *out = (T*)p;
+    return rc;
+  }
+  hipError_t event(hipEvent_t* out) {
+    const hipError_t rc = hipEventCreateWithFlags(out, hipEventDisableTiming);
+    if (rc == hipSuccess) events.push_back(*out);
+    return rc;
+  }
+};
+
+struct bc_engine {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  hipStream_t copy_stream = nullptr;
+  bc::HostDevPlan h;
+  bc::DevPlan* d_plan = nullptr;
+  std::vector<void*> allocs;
+  uint32_t* d_table = nullptr;
+  bool own_table = false;
+  uint64_t table_entries = 0;
+  uint32_t* d_bits = nullptr;   // two-level counting: the first-occurrence bit of every tuple (large dense tables)
+  uint64_t n_bit_words = 0;
+  bool bits_dirty = false;      // some bit may be set: fold before anyone reads the table
+  bool table_exposed = false;   // bc_engine_table_ptr has handed the table out: every sync folds, as for a caller's table
+  uint64_t dirty_bytes = 0;     // the dirty-block map behind the bit map (DevPlan::dirty_off): one flag per 64 entries
+  bool table_all_dirty = false; // somebody wrote the table without flagging (a fold, the wave-per-read kernel, a caller
+                                // holding its pointer): the next reset zeroes all of it
+  uint64_t reads_since_fold = 0;  // upper bound on the bits set since then: picks the fold kernel
+  // log-mode counting (bc_fold.h): BC_COUNT_LOG = 0 never | 1 whenever the plan allows it | auto (default): submits of
+  // at least log_min_reads reads (BC_COUNT_LOG_MIN_READS).  Either way the counts are the same.
+  int count_log = 2;
+  uint64_t log_min_reads = 1ull << 24;
+  uint64_t log_chunk = 1ull << 27;   // reads per match launch + fold (BC_COUNT_LOG_CHUNK, a multiple of 64)
+  bool log_hot = false;              // the hot-counter cache in log mode too (BC_COUNT_LOG_HOT=0|1; off: 4.62 vs 4.75 ms
+                                     // for config 3's match kernel -- the fold's LDS atomics take hot tuples in stride)
+  uint64_t log_cap = 0;              // entries allocated in d_log / d_grouped
+  uint32_t* d_log = nullptr;
+  uint32_t* d_grouped = nullptr;
+  uint64_t gz_blocks = 0;            // BGZF blocks inflated on the device for this engine (bc_engine_gz_blocks_inflated)
+  uint64_t log_folds = 0;            // folds run since the engine was created (bc_engine_count_log_folds)
+  uint32_t* d_fold_meta = nullptr;   // [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each
+  // What the last reset owes (settle_owed()): a reset only records it, and whoever touches table, dirty map or bit map
+  // next pays it first, on the engine's stream -- except a log-mode submit, whose match kernel touches none of them:
+  // there the table's part runs on reset_stream beside the match kernel and is joined before the fold
+  // (BC_COUNT_LOG_DEFER_RESET=0|1), and the fold takes the bit map as all zero without anyone writing the zeros first
+  // (bc_fold.h, a fresh fold; BC_COUNT_LOG_FRESH=0|1).  The table's part is only ever owed for a table nobody else can
+  // see (engine-owned, its pointer not handed out): whoever holds a pointer may order work after the reset by the stream.
+  bool owed_table = false;           // the dirty-block reset, or (owed_table_all) table and dirty map zeroed whole
+  bool owed_table_all = false;
+  bool owed_bits = false;            // the bit map zeroed
+  bool defer_reset = true;
+  bool fold_fresh = true;
+  hipStream_t reset_stream = nullptr;  // created with the first deferred reset
+  hipEvent_t reset_fork = nullptr, reset_join = nullptr;
+  unsigned long long* d_counters = nullptr;
+  uint32_t barcode_num = 0;
+  uint32_t n_sets[bc::kMaxGroups] = {0};
+  std::vector<std::vector<std::string>> set_seqs;  // per group: the known sequences in index order
+  bool has_sample_group = false;
+  uint8_t* trace_outcome = nullptr;
+  uint64_t* trace_idx = nullptr;
+  bool timing = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  std::vector<float> launch_ms;  // resolved launch times not yet handed out (bc_engine_kernel_ms[_each])
+  // compacted results
+  std::vector<uint64_t> row_idx;
+  std::vector<uint32_t> row_cnt;
+  // host staging (bc_engine_submit_host)
+  static constexpr int kStages = 2;
+  uint8_t* pin[kStages] = {nullptr, nullptr};
+  uint8_t* dev[kStages] = {nullptr, nullptr};
+  hipEvent_t copied[kStages] = {nullptr, nullptr};
+  hipEvent_t consumed[kStages] = {nullptr, nullptr};
+  size_t stage_bytes = 0;
+  uint32_t lds_limit = 0;
+  uint32_t n_cus = 0;
+  bc::JitKernels jit;  // scheme-specialised kernels, one per kernel shape (NW, NWW, lengths, tables, tracing)
+  uint64_t reads_seen = 0;  // reads submitted so far: a cache miss is only worth a compile for a long run
+  int jit_mode = 1;  // BC_JIT = 0: never | 1 (default): cache hit -> at once, else compiled in the background once 2^20
+                     // reads have been seen | force (2): always, compiled synchronously | cached (3): cache hits only
+  std::string last_kernel;
+  bool pipe = true;   // software-pipelined tile fetch (BC_PIPE=0|1)
+  int lhash_mode = 1; // LDS exact-match tables (PlanSetup::lhash_mode)
+  // random-barcode mode: the hash set of (tuple, random barcode) keys
+  unsigned long long* d_slots = nullptr;
+  uint32_t* d_vals = nullptr;  // sparse plans without a random barcode: the count of each key
+  uint64_t n_slots = 0;
+  uint32_t key_words = 1;      // u64 words per key: 1, or the plan's wide keys (bc_long.h)
+  uint32_t* d_ready = nullptr;  // wide keys: a slot's payload has been published
+  std::vector<uint64_t> row_wide;  // compacted rows of a wide-key plan: key_words words per row (row_idx stays empty)
+  uint64_t key_bound = 0;  // upper bound on the keys held: reads submitted / keys imported so far
+  // the wave-per-read kernel's plan (bc_long.h): built when a submit needs it -- reads above 320 bases -- or at
+  // creation when the lane-per-read kernel cannot run the plan at all (long_only)
+  bool long_only = false, long_ready = false;
+  bc::LongHost lh;
+  bc::LongPlan* d_long = nullptr;
+  const bc_plan* src_plan = nullptr;  // (the caller keeps the plan alive for the engine's lifetime)
+  // the label pool of the text renderer (bc_render.h), built at the first render: the IDs of the counted sets
+  bool render_pool_ready = false;
+  uint32_t* d_label_off = nullptr;
+  uint8_t* d_label_bytes = nullptr;
+  uint32_t label_off_start[bc::kMaxGroups] = {0};
+  uint32_t label_max[bc::kMaxGroups] = {0};  // the longest ID of each counted set
+  bool table_materialized = false;  // random-barcode plans: d_table holds the per-tuple distinct counts of the current
+                                    // key set (bc_engine_materialize_table), possibly summed over ranks since
+  // The enrichment renderer (bc_enrich_render.h).  counts_epoch moves whenever what bc_engine_finish would hand out may
+  // have changed (counts_changed()); the folded sums on the device are those of epoch sums_epoch and are served only
+  // while the two agree -- and never for a table somebody else may write (caller-owned, or its pointer handed out).
+  uint64_t counts_epoch = 1, sums_epoch = 0;
+  unsigned long long* d_sums = nullptr;  // S * SUM singles, then S * P doubles
+  uint64_t sums_passes = 0;              // table passes made for them since the engine was created
+  bool canon_ready = false;              // the canonical maps of the label pool have been built
+  uint32_t* d_canon = nullptr;           // canon[off_g + i]; NULL when no set shares an ID
+  // The raw-key renderer (bc_raw_render.h): the map's (key, count) pairs, re-keyed and sorted (bc_sort.h), kept on the
+  // device for the counts of epoch raw_epoch -- the S + 1 renders of one merged run sort once.  Whatever moves
+  // counts_epoch (submits, imports, resets, clear_keys, finish_all) retires them; the next render frees and rebuilds.
+  uint64_t raw_epoch = 0;
+  uint64_t* d_raw_keys = nullptr;
+  uint32_t* d_raw_cnts = nullptr;
+  uint64_t raw_n = 0;
+  uint64_t raw_sorts = 0;                // sorts made since the engine was created (bc_engine_raw_render_sorts)
+  float raw_sort_ms = 0.f;               // export + re-key + sort of the last one, from HIP events
+};
+
+namespace bc {
+
+// (defined in bc_engine.hip)
+uint32_t grid_for(uint64_t n);  // workgroups of 256 for a grid-stride loop over n items
+// src -> a device allocation the engine owns until it is freed; *out: its address
+int upload(bc_engine* e, const void* src, size_t bytes, uint64_t* out);
+// What every reader of a dense plan's counts does first (bc_engine_finish, bc_engine_enrich, the renderers): wait for the
+// submits, and for a random-barcode plan turn the key set into per-tuple counts unless that has been done for the
+// current keys.  Afterwards entry i counts table[i] + bit i of the bit map (when e->bits_dirty: two-level counting, not
+// folded).
+int dense_counts_ready(bc_engine* e);
+// The shape of a dense plan's enrichment (bc_engine_enrich); false + set_error() for plans that have none.
+bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples);
+// The (tuple key, count) pairs of a narrow-key map as they stand, into buffers that `g` owns: a random-barcode plan's key
+// set first aggregated into per-tuple distinct counts.  e->d_slots is not NULL; the stream has drained on return.
+int export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** d_key, uint32_t** d_cnt, uint64_t* n);
+
+}  // namespace bc
+
+#endif

@@ -1,7 +1,7 @@
 // bc_enrich_render.h -- the text of a dense plan's Single and Double enrichment files (bc_engine_render_enriched /
-// bc_engine_render_enriched_merged): the lane-level pieces, shared by the kernels of bc_enrich_render.hip and the host
-// harness tests/render/enrich_render_host.cpp (which runs this SAME code under AddressSanitizer; never a product path on
-// the host).
+// bc_engine_render_enriched_merged): the lane-level pieces, shared by the kernels of bc_text_kernels.h (instantiated in
+// bc_text.hip, next to the fold of the sums) and the host harness tests/render/enrich_render_host.cpp (which runs this
+// SAME code under AddressSanitizer; never a product path on the host).
 //
 // A line belongs to one key k of one sample's slice of the marginal sums (bc_engine_enrich's layout; G counted barcodes,
 // N_g = size of known set g, SUM = sum N_g, P = sum over pairs g < h of N_g * N_h, pairs in add_double's order):
@@ -182,20 +182,5 @@ BC_HD void text_line_write(const EnrichRenderView& v, uint64_t k, uint32_t len, 
 }
 
 }  // namespace bc
-
-#if defined(__HIPCC__)
-// The kernels (bc_enrich_render.hip); all enqueue on `stream`.  A block is kRenderBlock consecutive keys; the three
-// passes are those of bc_render.h.
-hipError_t bc_enrich_render_sizes_launch(const bc::EnrichRenderView& v, uint64_t n_blocks, uint32_t* d_rows,
-                                         unsigned long long* d_bytes, hipStream_t stream);
-hipError_t bc_enrich_render_lens_launch(const bc::EnrichRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len,
-                                        hipStream_t stream);
-hipError_t bc_enrich_render_write_launch(const bc::EnrichRenderView& v, uint64_t b0, uint64_t n_blocks, uint64_t lo, uint64_t hi,
-                                         const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
-                                         uint64_t out_cap, hipStream_t stream);
-// Folds the sums of one kind for n_samples samples (v.sums writable, v.canon not NULL): every key that is not its own
-// enrich_fold_target adds its sum to the target and becomes zero.
-hipError_t bc_enrich_fold_launch(const bc::EnrichRenderView& v, uint64_t n_samples, hipStream_t stream);
-#endif
 
 #endif

@@ -1,6 +1,7 @@
 // bc_raw_render.h -- the text of a raw-key plan's counts files (bc_engine_render_raw_counts / bc_engine_render_raw_merged):
-// the lane-level pieces, shared by the kernels of bc_raw_render.hip and the host harness
-// tests/render/raw_render_host.cpp (which runs this SAME code under AddressSanitizer; never a product path on the host).
+// the lane-level pieces, shared by the kernels of bc_text_kernels.h (instantiated in bc_text.hip, next to the re-key step)
+// and the host harness tests/render/raw_render_host.cpp (which runs this SAME code under AddressSanitizer; never a
+// product path on the host).
 //
 // A raw-key plan (bc_plan_mode() == 2) keeps some capture as it was read, so its rows have no table index; what the
 // device holds is a map of (key, count).  A key is a mixed-radix number over the scheme's groups: a known set gives its
@@ -189,19 +190,5 @@ BC_HD void text_line_write(const RawRenderView& v, uint64_t i, uint32_t len, Byt
 }
 
 }  // namespace bc
-
-#if defined(__HIPCC__)
-// The kernels (bc_raw_render.hip); all enqueue on `stream`.
-// keys[i] = s * t_space + T  (the engine's key: the sample group, when there is one, is its most significant digit)
-//   ->  T * S + s,  in place; S == 1: nothing to do, and nothing is launched
-hipError_t bc_raw_rekey_launch(uint64_t* d_keys, uint64_t n, uint64_t t_space, uint32_t S, hipStream_t stream);
-// the three passes of bc_text_kernels.h for this view (bc_render.h describes them)
-hipError_t bc_raw_render_sizes_launch(const bc::RawRenderView& v, uint64_t n_blocks, uint32_t* d_rows,
-                                      unsigned long long* d_bytes, hipStream_t stream);
-hipError_t bc_raw_render_lens_launch(const bc::RawRenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t stream);
-hipError_t bc_raw_render_write_launch(const bc::RawRenderView& v, uint64_t b0, uint64_t n_blocks, uint64_t lo, uint64_t hi,
-                                      const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
-                                      uint64_t out_cap, hipStream_t stream);
-#endif
 
 #endif

@@ -1,6 +1,6 @@
 // bc_render.h -- the text of a dense plan's counts files (bc_engine_render_counts / bc_engine_render_merged): the
-// lane-level pieces, shared by the kernels of bc_render.hip and the host harness tests/render/render_host.cpp (which
-// runs this SAME code under AddressSanitizer; never a product path on the host).
+// lane-level pieces, shared by the kernels of bc_text_kernels.h (instantiated in bc_text.hip) and the host harness
+// tests/render/render_host.cpp (which runs this SAME code under AddressSanitizer; never a product path on the host).
 //
 // A line belongs to one barcode tuple t in [0, T), T = N_0 * .. * N_{G-1} (the last counted barcode is the innermost
 // axis, as bc_engine_decode_index reads it), and to an ordered list of sample columns:
@@ -123,21 +123,5 @@ BC_HD void text_line_write(const RenderView& v, uint64_t t, uint32_t len, Byte* 
 }
 
 }  // namespace bc
-
-#if defined(__HIPCC__)
-// The kernels (bc_render.hip); all enqueue on `stream`.  A block is kRenderBlock consecutive tuples.
-constexpr uint32_t kRenderBlock = 1024;
-// pass 1: lines and text bytes of every block (both arrays zeroed by the caller)
-hipError_t bc_render_sizes_launch(const bc::RenderView& v, uint64_t n_blocks, uint32_t* d_rows, unsigned long long* d_bytes,
-                                  hipStream_t stream);
-// the line length of tuples lo .. lo + n - 1 (0: no line), for a block whose text has to be cut inside
-hipError_t bc_render_lens_launch(const bc::RenderView& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t stream);
-// pass 2: the lines of tuples [lo, hi) inside blocks b0 .. b0 + n_blocks - 1 into d_out; the text of block b starts at
-// d_prefix[b] - sub (d_prefix: exclusive scan of pass 1's bytes; tuples outside [lo, hi) take no room), nothing is
-// stored at or beyond out_cap
-hipError_t bc_render_write_launch(const bc::RenderView& v, uint64_t b0, uint64_t n_blocks, uint64_t lo, uint64_t hi,
-                                  const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,
-                                  uint64_t out_cap, hipStream_t stream);
-#endif
 
 #endif

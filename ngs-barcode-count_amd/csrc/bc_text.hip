@@ -1,0 +1,654 @@
+// bc_text.hip -- the output files written as CSV text on the device: the counts files of a dense plan
+// (bc_engine_render_counts / _merged; lane code bc_render.h), the Single and Double enrichment files
+// (bc_engine_render_enriched / _merged; bc_enrich_render.h) and the sorted counts files of a raw-key plan
+// (bc_engine_render_raw_counts / _merged; bc_raw_render.h, bc_sort.h).  A renderer is a view struct with lane code and a
+// front end that checks the request and fills the view; the kernels (bc_text_kernels.h) and the host loop around them
+// (stream_text) are templates over the view.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "bc_engine_impl.h"
+#include "bc_enrich_render.h"
+#include "bc_raw_render.h"
+#include "bc_sort.h"
+#include "bc_text_kernels.h"
+
+using namespace bc;
+
+// ---- what the three renderers share ----
+
+// The IDs of the counted sets on the device, once per engine: per group N_g + 1 offsets, and the bytes back to back.
+static int ensure_render_pool(bc_engine* e, const char* who) {
+  if (e->render_pool_ready) return BC_OK;
+  const uint32_t G = e->barcode_num;
+  std::vector<uint32_t> off;
+  std::string bytes;
+  try {
+    for (uint32_t g = 0; g < G; ++g) {
+      e->label_off_start[g] = (uint32_t)off.size();
+      e->label_max[g] = 0;
+      const uint32_t n = bc_plan_n_counted(e->src_plan, g);
+      for (uint32_t i = 0; i < n; ++i) {
+        const char* id = bc_plan_counted_id(e->src_plan, g, i);
+        const size_t len = id ? strlen(id) : 0;
+        if (bytes.size() + len > 0xFFFFFFF0ull || off.size() > 0xFFFFFFF0ull) {
+          set_error(std::string(who) + ": the IDs of the counted barcodes pass 4 GB");
+          return BC_ERR_UNSUPPORTED;
+        }
+        off.push_back((uint32_t)bytes.size());
+        if (len) bytes.append(id, len);
+        e->label_max[g] = std::max<uint32_t>(e->label_max[g], (uint32_t)len);
+      }
+      off.push_back((uint32_t)bytes.size());
+    }
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  // both parts in one allocation (offsets first: the bytes need no alignment), so a failure leaves nothing behind
+  const size_t off_bytes = off.size() * 4;
+  std::string image;
+  try {
+    image.assign((const char*)off.data(), off_bytes);
+    image += bytes;
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  void* d_pool = nullptr;
+  HIP_TRY(hipMalloc(&d_pool, image.size() ? image.size() : 16));
+  if (!image.empty()) {
+    const hipError_t hrc = hipMemcpy(d_pool, image.data(), image.size(), hipMemcpyHostToDevice);
+    if (hrc != hipSuccess) {
+      (void)hipFree(d_pool);
+      HIP_TRY(hrc);
+    }
+  }
+  try {
+    e->allocs.push_back(d_pool);
+  } catch (const std::bad_alloc&) {
+    (void)hipFree(d_pool);
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  e->d_label_off = (uint32_t*)d_pool;
+  e->d_label_bytes = (uint8_t*)d_pool + off_bytes;
+  e->render_pool_ready = true;
+  return BC_OK;
+}
+
+// The lines of the keys [0, n_keys) that have one, in ascending key order, handed to `fn` in chunks that end with a
+// line.  Pass 1 sizes every block of the key space, the host scans the sizes and cuts the space into ranges whose text
+// fits one staging buffer, pass 2 writes range after range into one of two buffers (device + pinned) while the host hands
+// on the range before.  A block whose text passes the buffer is cut between its lines from their lengths.  Device
+// memory: 2 x buffer + 12 bytes per block of 1024 keys.  max_line: no line is longer.
+template <class View>
+static int stream_text(bc_engine* e, const char* who, const View& v, uint64_t max_line, bc_text_fn fn, void* user,
+                       uint64_t* n_rows) {
+  const uint64_t n_keys = text_keys(v);
+  uint64_t cap = 64ull << 20;
+  if (const char* ev = getenv("BC_RENDER_CHUNK_BYTES")) {  // (a value that does not parse, or 0, leaves the default)
+    char* end = nullptr;
+    const unsigned long long x = strtoull(ev, &end, 0);
+    if (end != ev && *end == '\0' && x > 0) cap = x;
+  }
+  cap = std::max(cap, max_line);  // never smaller than the longest possible line: every line fits some chunk
+
+  ScratchGuard g;
+  const uint64_t n_blocks = (n_keys + kRenderBlock - 1) / kRenderBlock;
+  uint32_t* d_rows = nullptr;
+  unsigned long long* d_bytes = nullptr;
+  HIP_TRY(g.dmalloc(&d_rows, n_blocks * 4));
+  HIP_TRY(g.dmalloc(&d_bytes, (n_blocks + 1) * 8));
+  HIP_TRY(hipMemsetAsync(d_rows, 0, n_blocks * 4, e->stream));
+  HIP_TRY(hipMemsetAsync(d_bytes, 0, (n_blocks + 1) * 8, e->stream));
+  HIP_TRY(text_sizes_launch(v, n_blocks, d_rows, d_bytes, e->stream));
+  std::vector<uint32_t> rows;
+  std::vector<unsigned long long> prefix;
+  try {
+    rows.resize(n_blocks);
+    prefix.resize(n_blocks + 1);
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  HIP_TRY(hipMemcpyAsync(rows.data(), d_rows, n_blocks * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(prefix.data(), d_bytes, n_blocks * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  uint64_t total_rows = 0, total_bytes = 0;
+  for (uint64_t b = 0; b < n_blocks; ++b) {  // sizes -> exclusive scan, in place
+    const uint64_t x = prefix[b];
+    prefix[b] = total_bytes;
+    total_bytes += x;
+    total_rows += rows[b];
+  }
+  prefix[n_blocks] = total_bytes;
+  if (total_rows == 0) return BC_OK;
+  HIP_TRY(hipMemcpyAsync(d_bytes, prefix.data(), (n_blocks + 1) * 8, hipMemcpyHostToDevice, e->stream));
+
+  const uint64_t slot = std::min(cap, total_bytes);
+  const size_t slot_alloc = (size_t)((slot + 3) & ~3ull);
+  uint8_t* d_text[2] = {nullptr, nullptr};
+  uint8_t* h_text[2] = {nullptr, nullptr};
+  hipEvent_t landed[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; ++k) {
+    HIP_TRY(g.dmalloc(&d_text[k], slot_alloc));
+    HIP_TRY(g.hmalloc(&h_text[k], slot_alloc));
+    HIP_TRY(g.event(&landed[k]));
+    if (total_bytes <= cap) break;  // one range: one slot
+  }
+  uint32_t *d_len = nullptr, *h_len = nullptr;  // a block's line lengths, when one has to be cut inside
+  uint64_t pending[2] = {0, 0};
+  auto consume = [&](int k) -> int {
+    HIP_TRY(hipEventSynchronize(landed[k]));
+    if (pending[k] && fn((const char*)h_text[k], (size_t)pending[k], user) != 0) {
+      set_error(std::string(who) + ": stopped by the callback");
+      return BC_ERR_STATE;
+    }
+    return BC_OK;
+  };
+  int64_t seg = 0;
+  // one range: the lines of tuples [lo, hi) inside blocks [b0, b1), `bytes` of text that starts at scan position `sub`
+  auto emit = [&](uint64_t b0, uint64_t b1, uint64_t lo, uint64_t hi, uint64_t sub, uint64_t bytes) -> int {
+    const int k = (int)(seg & 1);
+    if (bytes) {
+      HIP_TRY(text_write_launch(v, b0, b1 - b0, lo, hi, d_rows, d_bytes, sub, d_text[k], slot, e->stream));
+      HIP_TRY(hipMemcpyAsync(h_text[k], d_text[k], bytes, hipMemcpyDeviceToHost, e->stream));
+    }
+    pending[k] = bytes;
+    HIP_TRY(hipEventRecord(landed[k], e->stream));
+    int r2 = BC_OK;
+    if (seg >= 1) r2 = consume(k ^ 1);
+    ++seg;
+    return r2;
+  };
+  auto run = [&]() -> int {
+    uint64_t b0 = 0;
+    while (b0 < n_blocks) {
+      uint64_t b1 = b0;
+      while (b1 < n_blocks && prefix[b1 + 1] - prefix[b0] <= slot) ++b1;
+      int r2;
+      if (b1 > b0) {
+        if (prefix[b1] == prefix[b0]) {  // (nothing but empty blocks)
+          b0 = b1;
+          continue;
+        }
+        r2 = emit(b0, b1, b0 * kRenderBlock, std::min<uint64_t>(n_keys, b1 * kRenderBlock), prefix[b0], prefix[b1] - prefix[b0]);
+        if (r2 != BC_OK) return r2;
+        b0 = b1;
+        continue;
+      }
+      // block b0 alone passes the buffer: cut it between its lines
+      if (!d_len) {
+        HIP_TRY(g.dmalloc(&d_len, kRenderBlock * 4));
+        HIP_TRY(g.hmalloc(&h_len, kRenderBlock * 4));
+      }
+      const uint64_t t0 = b0 * kRenderBlock;
+      const uint32_t n = (uint32_t)std::min<uint64_t>(kRenderBlock, n_keys - t0);
+      HIP_TRY(text_lens_launch(v, t0, n, d_len, e->stream));
+      HIP_TRY(hipMemcpyAsync(h_len, d_len, n * 4, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      uint32_t len[kRenderBlock];  // (a copy: h_len is reused by a later block while ranges are in flight)
+      memcpy(len, h_len, n * 4);
+      uint32_t i = 0;
+      while (i < n) {
+        uint64_t bytes = 0;
+        uint32_t j = i;
+        while (j < n && bytes + len[j] <= slot) bytes += len[j++];  // (a line always fits: slot >= max_line)
+        if (bytes && (r2 = emit(b0, b0 + 1, t0 + i, t0 + j, prefix[b0], bytes)) != BC_OK) return r2;
+        i = j;
+      }
+      ++b0;
+    }
+    return seg ? consume((int)((seg - 1) & 1)) : BC_OK;
+  };
+  const int rc = run();
+  (void)hipStreamSynchronize(e->stream);  // nothing of ours may still be writing the staging buffers when they go
+  if (rc == BC_OK && n_rows) *n_rows = total_rows;
+  return rc;
+}
+
+// What every front end refuses after its plan's shape: no callback, a sample list that is not there, a sample that the
+// plan does not have (S of them).
+static int check_request(const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, uint64_t S) {
+  if (!fn || (n_cols && !cols)) {
+    set_error(std::string(who) + ": null callback or sample list");
+    return BC_ERR_INVALID;
+  }
+  for (uint32_t c = 0; c < n_cols; ++c)
+    if (cols[c] >= S) {
+      set_error(std::string(who) + ": sample index " + std::to_string(cols[c]) + " of " + std::to_string(S));
+      return BC_ERR_INVALID;
+    }
+  return BC_OK;
+}
+
+static int check_max_line(const char* who, uint64_t max_line) {
+  if (max_line > kRenderMaxLine) {
+    set_error(std::string(who) + ": a line could be " + std::to_string(max_line) + " bytes long; the renderer takes " +
+              std::to_string(kRenderMaxLine));
+    return BC_ERR_UNSUPPORTED;
+  }
+  return BC_OK;
+}
+
+// the sample columns on the device, for the render's lifetime
+static int upload_cols(bc_engine* e, ScratchGuard& g, const uint32_t* cols, uint32_t n_cols, uint32_t*& d_cols) {
+  HIP_TRY(g.dmalloc(&d_cols, (size_t)n_cols * 4));
+  HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e->stream));
+  return BC_OK;
+}
+
+// ---- counts of a dense plan as text (bc_render.h) ----
+
+// The lines of the tuples for which some listed sample counts, in ascending tuple order (stream_text).
+static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, void* user,
+                       uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (P.sparse) {
+    set_error(std::string(who) + ": the plan keeps raw captures, whose rows are sequences, not indices: write them from "
+              "bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  static_assert(bc::kRenderMaxG >= kMaxGroups, "a plan's counted barcodes fit the view");
+  bc::RenderView v;
+  memset(&v, 0, sizeof v);
+  v.G = e->barcode_num;
+  v.T = 1;
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    v.n[g] = P.groups[g0 + g].n_refs;
+    v.T *= v.n[g];
+  }
+  const uint64_t S = v.T ? e->table_entries / v.T : 0;
+  int rc = check_request(who, cols, n_cols, fn, S);
+  if (rc) return rc;
+  if ((rc = dense_counts_ready(e)) != BC_OK) return rc;
+  if (n_cols == 0 || v.T == 0 || e->table_entries == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    if (bc_plan_n_counted(e->src_plan, g) != v.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
+      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+      return BC_ERR_STATE;
+    }
+    v.off_start[g] = e->label_off_start[g];
+    max_line += e->label_max[g];
+  }
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
+  v.table = e->d_table;
+  v.bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
+  v.cols = d_cols;
+  v.n_cols = n_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+extern "C" {
+
+int bc_engine_render_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_text(e, "bc_engine_render_counts", &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
+                            uint64_t* n_rows) {
+  return render_text(e, "bc_engine_render_merged", sample_idx, n_samples, fn, user, n_rows);
+}
+
+}  // extern "C"
+
+// ---- counts of a raw-key plan as text (bc_raw_render.h, bc_sort.h) ----
+
+namespace bc {
+
+// key = s * t_space + T  ->  T * S + s: the same digits, the sample's moved to the least significant place
+__global__ __launch_bounds__(256) void raw_rekey_kernel(unsigned long long* __restrict__ keys, uint64_t n, uint64_t t_space,
+                                                        uint32_t S) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += step) {
+    const unsigned long long k = keys[i];
+    const unsigned long long s = k / t_space;
+    keys[i] = (k - s * t_space) * S + s;
+  }
+}
+
+}  // namespace bc
+
+// keys[i] = s * t_space + T  (the engine's key: the sample group, when there is one, is its most significant digit)
+//   ->  T * S + s,  in place; S == 1: nothing to do, and nothing is launched
+static hipError_t raw_rekey_launch(uint64_t* d_keys, uint64_t n, uint64_t t_space, uint32_t S, hipStream_t stream) {
+  if (n == 0 || S <= 1 || t_space == 0) return hipSuccess;
+  hipLaunchKernelGGL(raw_rekey_kernel, dim3(grid_for(n)), dim3(256), 0, stream, (unsigned long long*)d_keys, n, t_space, S);
+  return hipGetLastError();
+}
+
+static void raw_sorted_drop(bc_engine* e) {
+  if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
+  if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
+  e->d_raw_keys = nullptr;
+  e->d_raw_cnts = nullptr;
+  e->raw_n = 0;
+  e->raw_epoch = 0;
+}
+
+// The pairs of the current counts, sorted into the order of the files, in e->d_raw_keys / d_raw_cnts (raw_n of them):
+// served as they are while the counts epoch stands, else exported from the map (export_pairs, as finish_sparse does),
+// re-keyed and sorted.  Device memory while it runs:
+// the map's export bound x 12 bytes (kept), the same again for the sort's other buffers and n / 2 bytes of histograms.
+static int ensure_raw_sorted(bc_engine* e, uint64_t t_space, uint32_t S) {
+  if (e->raw_epoch == e->counts_epoch) return BC_OK;
+  raw_sorted_drop(e);
+  if (!e->d_slots) {  // nothing was ever submitted or imported
+    e->raw_epoch = e->counts_epoch;
+    return BC_OK;
+  }
+  ScratchGuard g;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIP_TRY(hipEventCreate(&ev0));
+  g.events.push_back(ev0);
+  HIP_TRY(hipEventCreate(&ev1));
+  g.events.push_back(ev1);
+  HIP_TRY(hipEventRecord(ev0, e->stream));
+  uint64_t* d_key = nullptr;
+  uint32_t* d_cnt = nullptr;
+  uint64_t n = 0;
+  const int rc = export_pairs(e, "raw render", g, &d_key, &d_cnt, &n);
+  if (rc != BC_OK) return rc;
+  if (n) {
+    uint64_t* d_key2 = nullptr;
+    uint32_t *d_cnt2 = nullptr, *d_scratch = nullptr;
+    HIP_TRY(g.dmalloc(&d_key2, n * 8));
+    HIP_TRY(g.dmalloc(&d_cnt2, n * 4));
+    HIP_TRY(g.dmalloc(&d_scratch, bc::sort_scratch_words(n) * 4));
+    HIP_TRY(raw_rekey_launch(d_key, n, t_space, S, e->stream));
+    uint32_t key_bits = 1;  // the bit length of the largest key of the space (the re-keyed digits have the same radices)
+    while (key_bits < 64 && ((e->h.table_entries - 1) >> key_bits) != 0) ++key_bits;
+    const hipError_t src = bc::sort_pairs_launch(e->stream, d_key, d_cnt, d_key2, d_cnt2, n, key_bits, d_scratch);
+    if (src == hipErrorInvalidValue) {
+      set_error("raw render: " + std::to_string(n) + " rows pass what one sort takes (2^32); write them from bc_engine_row_text on the host");
+      return BC_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(src);
+  }
+  HIP_TRY(hipEventRecord(ev1, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  (void)hipEventElapsedTime(&e->raw_sort_ms, ev0, ev1);
+  for (void* keep : {(void*)d_key, (void*)d_cnt}) g.dev.erase(std::find(g.dev.begin(), g.dev.end(), keep));
+  e->d_raw_keys = d_key;
+  e->d_raw_cnts = d_cnt;
+  e->raw_n = n;
+  e->raw_epoch = e->counts_epoch;
+  ++e->raw_sorts;
+  return BC_OK;
+}
+
+static int render_raw(bc_engine* e, const char* who, bool merged, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
+                      void* user, uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (!P.sparse) {
+    set_error(std::string(who) + ": the plan has a dense table: its files come from bc_engine_render_counts / "
+              "bc_engine_render_merged");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->key_words > 1) {
+    set_error(std::string(who) + ": the plan's keys are " + std::to_string(e->key_words) +
+              " words wide; write its rows from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
+    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: write the rows "
+              "from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  const uint32_t S = g0 ? P.groups[0].n_refs : 1u;
+  const uint64_t t_space = g0 ? P.groups[0].table_stride : e->h.table_entries;
+  int rc = check_request(who, cols, n_cols, fn, S);
+  if (rc) return rc;
+  bc::RawRenderView v;
+  memset(&v, 0, sizeof v);
+  v.G = e->barcode_num;
+  v.S = S;
+  v.merged = merged ? 1u : 0u;
+  v.sample = n_cols ? cols[0] : 0u;
+  v.n_cols = n_cols;
+  if (v.G > (uint32_t)bc::kRenderMaxG || g0 + v.G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
+    set_error(std::string(who) + ": the plan's groups do not fit the view");
+    return BC_ERR_STATE;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if ((rc = bc_engine_sync(e)) != BC_OK) return rc;  // the submits, as bc_engine_finish waits for them
+  if ((rc = ensure_raw_sorted(e, t_space, S)) != BC_OK) return rc;
+  if (n_cols == 0 || e->raw_n == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    const DevGroup& G = P.groups[g0 + g];
+    if (G.mode == kSetNone) {
+      v.raw_len[g] = G.len;
+      v.radix[g] = 1;
+      for (uint32_t k = 0; k < G.len; ++k) v.radix[g] *= 5;
+      max_line += G.len;
+    } else {
+      if (bc_plan_n_counted(e->src_plan, g) != G.n_refs) {  // (cannot happen: the key's digits are the plan's sets)
+        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+        return BC_ERR_STATE;
+      }
+      v.radix[g] = G.n_refs;
+      v.off_start[g] = e->label_off_start[g];
+      max_line += e->label_max[g];
+    }
+  }
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
+  v.keys = e->d_raw_keys;
+  v.cnts = e->d_raw_cnts;
+  v.n = e->raw_n;
+  v.cols = d_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+extern "C" {
+
+int bc_engine_render_raw_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_raw(e, "bc_engine_render_raw_counts", false, &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_raw_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
+                                uint64_t* n_rows) {
+  return render_raw(e, "bc_engine_render_raw_merged", true, sample_idx, n_samples, fn, user, n_rows);
+}
+
+int bc_engine_raw_render_sorts(const bc_engine* e, uint64_t* n) {
+  *n = e->raw_sorts;
+  return BC_OK;
+}
+
+int bc_engine_raw_render_sort_ms(const bc_engine* e, double* ms) {
+  *ms = (double)e->raw_sort_ms;
+  return BC_OK;
+}
+
+}  // extern "C"
+
+// ---- Single / Double enrichment as text (bc_enrich_render.h) ----
+
+namespace {
+
+// One key per lane, grid-stride over S * K entries.  A key that is not canonical moves its sum to the canonical one: an
+// entry is either only added to (canonical) or only read and zeroed by its own lane (the others), so no order matters.
+__global__ __launch_bounds__(256) void enrich_fold_kernel(bc::EnrichRenderView v, uint64_t n_samples) {
+  unsigned long long* sums = const_cast<unsigned long long*>(v.sums);
+  const uint64_t total = n_samples * v.K, step = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
+    const unsigned long long x = sums[e];
+    if (!x) continue;
+    const uint64_t s = e / v.K, k = e - s * v.K;
+    const uint64_t t = bc::enrich_fold_target(v, k);
+    if (t == k) continue;
+    atomicAdd(sums + s * v.K + t, x);
+    sums[e] = 0ull;
+  }
+}
+
+}  // namespace
+
+// Folds the sums of one kind for n_samples samples (v.sums writable, v.canon not NULL): every key that is not its own
+// enrich_fold_target adds its sum to the target and becomes zero.
+static hipError_t enrich_fold_launch(const bc::EnrichRenderView& v, uint64_t n_samples, hipStream_t stream) {
+  const uint64_t total = n_samples * v.K;
+  if (total == 0 || !v.canon) return hipSuccess;
+  hipLaunchKernelGGL(enrich_fold_kernel, dim3(grid_for(total)), dim3(256), 0, stream, v, n_samples);
+  return hipGetLastError();
+}
+
+// For every counted set, which entries share an ID: canon[off_g + i] = the smallest index of set g whose ID equals i's.
+// Built once per engine, next to the label pool; uploaded only when some set does share an ID.
+static int ensure_canon(bc_engine* e, const char* who) {
+  if (e->canon_ready) return BC_OK;
+  std::vector<uint32_t> canon;
+  bool shared = false;
+  try {
+    for (uint32_t g = 0; g < e->barcode_num; ++g) {
+      std::unordered_map<std::string, uint32_t> first;
+      const uint32_t n = bc_plan_n_counted(e->src_plan, g);
+      for (uint32_t i = 0; i < n; ++i) {
+        const char* id = bc_plan_counted_id(e->src_plan, g, i);
+        const uint32_t c = first.emplace(id ? id : "", i).first->second;
+        shared = shared || c != i;
+        canon.push_back(c);
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(who) + ": out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  if (shared) {
+    uint64_t d = 0;
+    const int rc = upload(e, canon.data(), canon.size() * 4, &d);
+    if (rc != BC_OK) return rc;
+    e->d_canon = (uint32_t*)(uintptr_t)d;
+  }
+  e->canon_ready = true;
+  return BC_OK;
+}
+
+// the view of one kind over the engine's sums (cols / n_cols left to the caller)
+static bc::EnrichRenderView enrich_view(const bc_engine* e, const EnrichShape& sh, uint64_t S, uint32_t kind) {
+  bc::EnrichRenderView v;
+  memset(&v, 0, sizeof v);
+  v.kind = kind;
+  v.G = sh.G;
+  v.K = kind == bc::kEnrichSingle ? sh.sum_n : sh.pairs;
+  v.sums = e->d_sums + (kind == bc::kEnrichSingle ? 0 : S * sh.sum_n);
+  v.canon = e->d_canon;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+  for (uint32_t g = 0; g < sh.G; ++g) {
+    v.n[g] = sh.n[g];
+    v.off_start[g] = e->label_off_start[g];
+  }
+  return v;
+}
+
+// The folded sums of the counts as they stand, on the device: computed by one pass over the table (bc_enrich_launch) and
+// the fold, then kept until the counts may have changed (counts_epoch).
+static int ensure_sums(bc_engine* e, const EnrichShape& sh, uint64_t S) {
+  const bool keep = e->own_table && !e->table_exposed;  // (nobody else can write the table between two renders)
+  if (e->d_sums && keep && e->sums_epoch == e->counts_epoch) return BC_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t n_single = S * sh.sum_n, n_double = S * sh.pairs;
+  e->sums_epoch = 0;
+  if (!e->d_sums) HIP_TRY(hipMalloc((void**)&e->d_sums, (size_t)(n_single + n_double) * 8));
+  HIP_TRY(hipMemsetAsync(e->d_sums, 0, (size_t)(n_single + n_double) * 8, e->stream));
+  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, e->d_sums,
+                           n_double ? e->d_sums + n_single : nullptr, e->stream));
+  if (e->d_canon) {
+    HIP_TRY(enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichSingle), S, e->stream));
+    if (n_double) HIP_TRY(enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichDouble), S, e->stream));
+  }
+  ++e->sums_passes;
+  if (keep) e->sums_epoch = e->counts_epoch;
+  return BC_OK;
+}
+
+static int render_enriched(bc_engine* e, const char* who, int kind, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
+                           void* user, uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  EnrichShape sh;
+  uint64_t S = 0;
+  if (!enrich_shape(e, who, &sh, &S)) return BC_ERR_UNSUPPORTED;
+  if (kind != BC_ENRICH_SINGLE && kind != BC_ENRICH_DOUBLE) {
+    set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
+    return BC_ERR_INVALID;
+  }
+  int rc = check_request(who, cols, n_cols, fn, S);
+  if (rc) return rc;
+  if ((rc = dense_counts_ready(e)) != BC_OK) return rc;
+  const uint64_t K = kind == BC_ENRICH_SINGLE ? sh.sum_n : sh.pairs;  // (no pairs below three counted barcodes)
+  if (n_cols == 0 || K == 0 || e->table_entries == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  if ((rc = ensure_canon(e, who)) != BC_OK) return rc;
+  uint32_t longest[2] = {0, 0};  // the two longest IDs of different sets
+  for (uint32_t g = 0; g < sh.G; ++g) {
+    if (bc_plan_n_counted(e->src_plan, g) != sh.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
+      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+      return BC_ERR_STATE;
+    }
+    const uint32_t m = e->label_max[g];
+    if (m > longest[0]) {
+      longest[1] = longest[0];
+      longest[0] = m;
+    } else if (m > longest[1]) {
+      longest[1] = m;
+    }
+  }
+  const uint64_t max_line = 1 + (sh.G - 1) + 21ull * n_cols + longest[0] + (kind == BC_ENRICH_DOUBLE ? longest[1] : 0u);
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
+  if ((rc = ensure_sums(e, sh, S)) != BC_OK) return rc;
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
+  bc::EnrichRenderView v = enrich_view(e, sh, S, (uint32_t)kind);
+  v.cols = d_cols;
+  v.n_cols = n_cols;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+extern "C" {
+
+int bc_engine_render_enriched(bc_engine* e, int kind, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_enriched(e, "bc_engine_render_enriched", kind, &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_enriched_merged(bc_engine* e, int kind, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn,
+                                     void* user, uint64_t* n_rows) {
+  return render_enriched(e, "bc_engine_render_enriched_merged", kind, sample_idx, n_samples, fn, user, n_rows);
+}
+
+int bc_engine_enrich_render_passes(const bc_engine* e, uint64_t* n) {
+  *n = e->sums_passes;
+  return BC_OK;
+}
+
+}  // extern "C"

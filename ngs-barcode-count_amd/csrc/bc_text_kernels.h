@@ -1,9 +1,11 @@
 // bc_text_kernels.h -- the kernels that turn a key space into text lines, for every view that has lane code for it
-// (bc_render.h: the counts files; bc_enrich_render.h: the Single / Double files).  A view V gives, in namespace bc,
+// (bc_render.h: the counts files; bc_enrich_render.h: the Single / Double files; bc_raw_render.h: the counts files of a
+// raw-key plan).  A view V gives, in namespace bc,
 //     text_keys(v)                         the number of keys
 //     text_line_len(v, k)                  bytes of key k's line, 0: no line
 //     text_line_write(v, k, len, dst, at, win)   the part of the line inside a window
-// Device code only; included by the .hip file that instantiates the kernels for its view.
+// Device code and its launchers, all enqueueing on `stream`; included by bc_text.hip, which instantiates them for the
+// three views.
 //
 // A workgroup of four wavefronts owns a block of 1024 consecutive keys, a wavefront four chunks of 64 (one key per
 // lane, so every column's read is coalesced).  Chunks without a line are skipped by ballot.
@@ -26,6 +28,7 @@
 
 namespace bc {
 
+constexpr uint32_t kRenderBlock = 1024;       // a block: as many consecutive keys
 constexpr uint32_t kWaves = 4, kChunks = 4;   // wavefronts per workgroup, chunks per wavefront
 constexpr uint32_t kWinBytes = 4096;           // one wavefront's staging window
 static_assert(kWaves * kChunks * 64 == kRenderBlock, "a workgroup owns one block");
@@ -130,6 +133,7 @@ __global__ __launch_bounds__(256) void text_write_kernel(View v, uint64_t b0, ui
   }
 }
 
+// pass 1: lines and text bytes of every block (both arrays zeroed by the caller)
 template <class View>
 hipError_t text_sizes_launch(const View& v, uint64_t n_blocks, uint32_t* d_rows, unsigned long long* d_bytes,
                              hipStream_t stream) {
@@ -139,6 +143,7 @@ hipError_t text_sizes_launch(const View& v, uint64_t n_blocks, uint32_t* d_rows,
   return hipGetLastError();
 }
 
+// the line length of keys lo .. lo + n - 1 (0: no line), for a block whose text has to be cut inside
 template <class View>
 hipError_t text_lens_launch(const View& v, uint64_t lo, uint32_t n, uint32_t* d_len, hipStream_t stream) {
   if (n == 0) return hipSuccess;
@@ -146,6 +151,9 @@ hipError_t text_lens_launch(const View& v, uint64_t lo, uint32_t n, uint32_t* d_
   return hipGetLastError();
 }
 
+// pass 2: the lines of keys [lo, hi) inside blocks b0 .. b0 + n_blocks - 1 into d_out; the text of block b starts at
+// d_prefix[b] - sub (d_prefix: exclusive scan of pass 1's bytes; keys outside [lo, hi) take no room), nothing is stored
+// at or beyond out_cap
 template <class View>
 hipError_t text_write_launch(const View& v, uint64_t b0, uint64_t n_blocks, uint64_t lo, uint64_t hi,
                              const uint32_t* d_rows, const unsigned long long* d_prefix, uint64_t sub, uint8_t* d_out,

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ngs-barcode-count_amd", "csrc")
 EXE = os.path.join(ROOT, "tests", "render", "raw_render_host")
 SRC = os.path.join(ROOT, "tests", "render", "raw_render_host.cpp")
-DEPS = [SRC] + [os.path.join(CSRC, h) for h in ("bc_raw_render.h", "bc_render.h", "bc_intrin.h")]
+DEPS = [SRC, os.path.join(ROOT, "tests", "render", "stage_check.h")] + [
+    os.path.join(CSRC, h) for h in ("bc_raw_render.h", "bc_render.h", "bc_intrin.h")]
 BASES = "ACTGN"
 
 

@@ -8,9 +8,7 @@
 // OUT: u64 lines, u64 bytes, then the text of the keys 0 .. K-1 for those columns.
 //
 // With has_canon the sums are folded first, key by key, through enrich_fold_target.  Then every line is written twice,
-// as tests/render/render_host.cpp does: whole, into a heap block of exactly enrich_row_len bytes, and the way a
-// wavefront stages it -- the lines of 64 keys laid end to end from position `pad`, cut into windows of `win` bytes that
-// are heap blocks of their own.  Both texts must agree.
+// whole and staged through windows, and both texts must agree (stage_check.h).
 // Exit status 0: ran; 2: bad arguments; 3: the length predicted and the bytes written differ; 4: the windowed text
 // differs from the whole one; 5: a key does not decode to itself.
 #include <stdint.h>
@@ -22,6 +20,7 @@
 #include <vector>
 
 #include "../../ngs-barcode-count_amd/csrc/bc_enrich_render.h"
+#include "stage_check.h"
 
 static bool rd(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
 
@@ -111,52 +110,10 @@ int main(int argc, char** argv) {
         sums[s * v.K + k] = 0;
       }
 
-  std::string whole;
-  std::vector<uint32_t> lens(v.K);
-  uint64_t lines = 0;
-  for (uint64_t k = 0; k < v.K; ++k) {
-    const uint32_t len = lens[k] = bc::enrich_row_len(v, k);
-    if (!len) continue;
-    ++lines;
-    uint8_t* row = (uint8_t*)calloc(len, 1);
-    bc::enrich_row_write(v, k, len, row, 0, len);
-    if (memchr(row, 0, len) || row[len - 1] != '\n') return 3;
-    whole.append((const char*)row, len);
-    free(row);
-  }
-  // the way a wavefront stages 64 lines: window coordinates start at `pad`
-  std::string staged;
-  for (uint64_t c0 = 0; c0 < v.K; c0 += 64) {
-    const uint64_t c1 = c0 + 64 < v.K ? c0 + 64 : v.K;
-    uint64_t tot = 0;
-    for (uint64_t k = c0; k < c1; ++k) tot += lens[k];
-    if (!tot) continue;
-    for (uint64_t w0 = 0; w0 < pad + tot; w0 += win) {
-      uint8_t* wb = (uint8_t*)calloc(win, 1);
-      uint64_t start = pad;
-      for (uint64_t k = c0; k < c1; ++k) {
-        if (lens[k] && start < w0 + win && start + lens[k] > w0)
-          bc::enrich_row_write(v, k, lens[k], wb, (int64_t)start - (int64_t)w0, win);
-        start += lens[k];
-      }
-      const uint64_t a = w0 > pad ? w0 : pad, e = pad + tot < w0 + win ? pad + tot : w0 + win;
-      if (a < e) {  // (a window smaller than the pad holds no text at all)
-        if (memchr(wb + (a - w0), 0, e - a)) return 3;
-        staged.append((const char*)wb + (a - w0), e - a);
-      }
-      free(wb);
-    }
-  }
-  if (staged != whole) return 4;
+  const int rc = stage_check(v, win, pad, argv[2]);
   free(sums);
   free(canon);
   free(d_off);
   free(d_bytes);
-  f = fopen(argv[2], "wb");
-  if (!f) return 2;
-  const uint64_t out_head[2] = {lines, whole.size()};
-  fwrite(out_head, 8, 2, f);
-  fwrite(whole.data(), 1, whole.size(), f);
-  fclose(f);
-  return 0;
+  return rc;
 }

@@ -7,9 +7,7 @@
 //      known group (raw_len 0), n_ids x {u32 len, bytes}; n_cols x u32 column; n x u64 sorted keys T * S + s; n x u32 counts.
 // OUT: u64 lines, u64 bytes, then the text of the positions 0 .. n-1 for that view.
 //
-// Every line is written twice: whole, into a heap block of exactly raw_row_len bytes (AddressSanitizer sees a byte
-// outside it, a NUL left in it is a byte not written), and the way a wavefront stages it -- the lines laid end to end
-// from position `pad`, cut into windows of `win` bytes that are heap blocks of their own.  Both texts must agree.
+// Every line is written twice, whole and staged through windows, and both texts must agree (stage_check.h).
 // Exit status 0: ran; 2: bad arguments; 3: the length predicted and the bytes written differ; 4: the windowed text
 // differs from the whole one.
 #include <stdint.h>
@@ -21,6 +19,7 @@
 #include <vector>
 
 #include "../../ngs-barcode-count_amd/csrc/bc_raw_render.h"
+#include "stage_check.h"
 
 static bool rd(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
 
@@ -84,52 +83,11 @@ int main(int argc, char** argv) {
   v.label_off = d_off;
   v.label_bytes = d_bytes;
 
-  std::string whole;
-  std::vector<uint32_t> lens(n);
-  uint64_t lines = 0;
-  for (uint64_t t = 0; t < n; ++t) {
-    const uint32_t len = lens[t] = bc::raw_row_len(v, t);
-    if (!len) continue;
-    ++lines;
-    uint8_t* row = (uint8_t*)calloc(len, 1);
-    bc::raw_row_write(v, t, len, row, 0, len);
-    if (memchr(row, 0, len) || row[len - 1] != '\n') return 3;
-    whole.append((const char*)row, len);
-    free(row);
-  }
-  // the way a wavefront stages 64 lines: window coordinates start at `pad`
-  std::string staged;
-  for (uint64_t c0 = 0; c0 < n; c0 += 64) {
-    const uint64_t c1 = c0 + 64 < n ? c0 + 64 : n;
-    uint64_t tot = 0;
-    for (uint64_t t = c0; t < c1; ++t) tot += lens[t];
-    for (uint64_t w0 = 0; w0 < pad + tot; w0 += win) {
-      uint8_t* wb = (uint8_t*)calloc(win, 1);
-      uint64_t start = pad;
-      for (uint64_t t = c0; t < c1; ++t) {
-        if (lens[t] && start < w0 + win && start + lens[t] > w0)
-          bc::raw_row_write(v, t, lens[t], wb, (int64_t)start - (int64_t)w0, win);
-        start += lens[t];
-      }
-      const uint64_t a = w0 > pad ? w0 : pad, e = pad + tot < w0 + win ? pad + tot : w0 + win;
-      if (a < e) {  // (a window smaller than the pad holds no text at all)
-        if (memchr(wb + (a - w0), 0, e - a)) return 3;
-        staged.append((const char*)wb + (a - w0), e - a);
-      }
-      free(wb);
-    }
-  }
-  if (staged != whole) return 4;
+  const int rc = stage_check(v, win, pad, argv[2]);
   free(cols);
   free(keys);
   free(cnts);
   free(d_off);
   free(d_bytes);
-  f = fopen(argv[2], "wb");
-  if (!f) return 2;
-  const uint64_t out_head[2] = {lines, whole.size()};
-  fwrite(out_head, 8, 2, f);
-  fwrite(whole.data(), 1, whole.size(), f);
-  fclose(f);
-  return 0;
+  return rc;
 }

@@ -6,9 +6,7 @@
 //      {u32 len, bytes}, S * T x u32 table, and with has_bits (S * T + 31) / 32 x u32 bit map.
 // OUT: u64 lines, u64 bytes, then the text of the tuples 0 .. T-1 for those columns.
 //
-// Every line is written twice: whole, into a heap block of exactly render_row_len bytes (AddressSanitizer sees a byte
-// outside it, a NUL left in it is a byte not written), and the way a wavefront stages it -- the lines laid end to end
-// from position `pad`, cut into windows of `win` bytes that are heap blocks of their own.  Both texts must agree.
+// Every line is written twice, whole and staged through windows, and both texts must agree (stage_check.h).
 // Exit status 0: ran; 2: bad arguments; 3: the length predicted and the bytes written differ; 4: the windowed text
 // differs from the whole one.
 #include <stdint.h>
@@ -20,6 +18,7 @@
 #include <vector>
 
 #include "../../ngs-barcode-count_amd/csrc/bc_render.h"
+#include "stage_check.h"
 
 static bool rd(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
 
@@ -76,51 +75,10 @@ int main(int argc, char** argv) {
   v.label_off = d_off;
   v.label_bytes = d_bytes;
 
-  std::string whole;
-  std::vector<uint32_t> lens(v.T);
-  uint64_t lines = 0;
-  for (uint64_t t = 0; t < v.T; ++t) {
-    const uint32_t len = lens[t] = bc::render_row_len(v, t);
-    if (!len) continue;
-    ++lines;
-    uint8_t* row = (uint8_t*)calloc(len, 1);
-    bc::render_row_write(v, t, len, row, 0, len);
-    if (memchr(row, 0, len) || row[len - 1] != '\n') return 3;
-    whole.append((const char*)row, len);
-    free(row);
-  }
-  // the way a wavefront stages 64 lines: window coordinates start at `pad`
-  std::string staged;
-  for (uint64_t c0 = 0; c0 < v.T; c0 += 64) {
-    const uint64_t c1 = c0 + 64 < v.T ? c0 + 64 : v.T;
-    uint64_t tot = 0;
-    for (uint64_t t = c0; t < c1; ++t) tot += lens[t];
-    for (uint64_t w0 = 0; w0 < pad + tot; w0 += win) {
-      uint8_t* wb = (uint8_t*)calloc(win, 1);
-      uint64_t start = pad;
-      for (uint64_t t = c0; t < c1; ++t) {
-        if (lens[t] && start < w0 + win && start + lens[t] > w0)
-          bc::render_row_write(v, t, lens[t], wb, (int64_t)start - (int64_t)w0, win);
-        start += lens[t];
-      }
-      const uint64_t a = w0 > pad ? w0 : pad, e = pad + tot < w0 + win ? pad + tot : w0 + win;
-      if (a < e) {  // (a window smaller than the pad holds no text at all)
-        if (memchr(wb + (a - w0), 0, e - a)) return 3;
-        staged.append((const char*)wb + (a - w0), e - a);
-      }
-      free(wb);
-    }
-  }
-  if (staged != whole) return 4;
+  const int rc = stage_check(v, win, pad, argv[2]);
   free(table);
   free(bits);
   free(d_off);
   free(d_bytes);
-  f = fopen(argv[2], "wb");
-  if (!f) return 2;
-  const uint64_t out_head[2] = {lines, whole.size()};
-  fwrite(out_head, 8, 2, f);
-  fwrite(whole.data(), 1, whole.size(), f);
-  fclose(f);
-  return 0;
+  return rc;
 }

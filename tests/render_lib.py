@@ -9,7 +9,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ngs-barcode-count_amd", "csrc")
 EXE = os.path.join(ROOT, "tests", "render", "render_host")
 SRC = os.path.join(ROOT, "tests", "render", "render_host.cpp")
-DEPS = [SRC, os.path.join(CSRC, "bc_render.h"), os.path.join(CSRC, "bc_intrin.h")]
+DEPS = [SRC, os.path.join(ROOT, "tests", "render", "stage_check.h"), os.path.join(CSRC, "bc_render.h"),
+        os.path.join(CSRC, "bc_intrin.h")]
 
 
 def exe():

@@ -138,6 +138,43 @@ def test_random_barcode_known_sample_raw_counted():
     eng.close()
 
 
+def _parsed(eng):
+    """every sample's text read back as sorted (sample index, "f_0,f_1,..", count)"""
+    out = []
+    for s in range(n_samples_of(eng.plan)):
+        for line in eng.render_raw_counts(s).decode().split("\n")[:-1]:
+            fields, cnt = line.rsplit(",", 1)
+            out.append((s, fields, int(cnt)))
+    return sorted(out)
+
+
+def _rows_as_parsed(plan, rows):
+    """finish()'s rows in the same form: the sample as its index, a known group's sequence as its ID"""
+    samples = {x: i for i, (x, _) in enumerate(plan.samples())} if plan.sample_barcode else {}
+    ids = [dict(plan.counted(g)) for g in range(plan.barcode_num)]
+    return sorted((samples[s] if samples else 0, ",".join(ids[g].get(x, x) for g, x in enumerate(t.split(","))), n)
+                  for s, t, n in rows)
+
+
+@pytest.mark.parametrize("make", [lambda: cases.build_case("raw_counted", seed=29, n=4000), rrc.random_raw_case],
+                         ids=["raw_counted", "random_raw"])
+def test_finish_and_render_share_one_export(make):
+    """bc_engine_finish and the raw-key render read the key map through the same export: either order gives the same
+    rows, and a finish between two renders neither changes them nor costs a second sort"""
+    c = make()
+    a, b = run(c), run(c)
+    assert a.plan.mode == "sparse" and key_words(a) == 1
+    rows = a.result_rows()  # finish first ..
+    assert len(rows) > 20 and _parsed(a) == _rows_as_parsed(a.plan, rows)
+    first = _parsed(b)      # .. and, on a fresh engine, the render first
+    assert b.result_rows() == rows and first == _rows_as_parsed(b.plan, rows)
+    assert b.result_rows() == rows  # a second finish after the render
+    assert _parsed(b) == first and b.raw_render_sorts() == 1  # render, finish, render, no submit between: one sort
+    assert a.raw_render_sorts() == 1
+    a.close()
+    b.close()
+
+
 def test_imported_keys_at_the_ends_of_the_space():
     """hand-made keys through bc_engine_import_counts: the smallest and largest key of the space, counts 1 and 2^32-1"""
     import torch
