@@ -494,6 +494,45 @@ int bc_bgzf_inflate_device(int device_id, void *hip_stream, const void *d_src, u
  * wait for the device. */
 int bc_engine_gz_blocks_inflated(const bc_engine *e, uint64_t *n);
 
+/* ---- ordinary gzip: one long deflate stream, inflated on the device in segments ------------------ */
+
+/* What gzip, pigz and a sequencer's converter write is one deflate stream per member, with no index: there is no way
+ * into its middle but to search for block headers.  A SPAN of such a stream -- compressed bytes, a start bit that is a
+ * known block boundary, the 32 KiB of text before it -- is inflated in five stages: a wavefront per partition of
+ * part_bytes compressed bytes finds the first offset at which a dynamic block header passes the decoder's checks; a
+ * wavefront per candidate decodes without storing until it lands on a later candidate; the host follows those links
+ * from the start bit (segments on the path are real, every other candidate is false); a wavefront per segment decodes
+ * again with markers for the bytes before its start; the markers are resolved segment by segment, then all at once.
+ * Opt-in for bc_fastq_count*: BC_GZ_DEVICE=all sends a .gz file that is not BGZF this way (BC_GZ_SPAN_BYTES and
+ * BC_GZ_PART_BYTES size the spans and partitions); counts are the same either way. */
+
+#define BC_GUNZIP_OK 0
+#define BC_GUNZIP_OUTPUT_FULL 1  /* the text does not fit: text_bytes / end_bit give the last block boundary that does */
+#define BC_GUNZIP_BAD_STREAM 2   /* not a deflate stream: `detail` is a BC_INFLATE_* word */
+
+typedef struct bc_gunzip_result {
+  uint32_t status;      /* BC_GUNZIP_* */
+  uint32_t detail;
+  uint64_t text_bytes;  /* bytes of text written to d_text (BC_GUNZIP_OUTPUT_FULL: that would fit; none are written) */
+  uint64_t end_bit;     /* the block boundary the text ends at, in bits of d_src; == start_bit: no whole block */
+  uint32_t member_end;  /* 1: that boundary is the end of the member's last block (the trailer follows, byte aligned) */
+  uint32_t segments;    /* verified segments */
+  uint32_t rejected;    /* candidates the chain walked past without landing on them (false block headers) */
+  uint32_t crc32;       /* CRC-32 of the text written */
+} bc_gunzip_result;
+
+/* Inflates the whole blocks of d_src[0, src_bytes) (device memory, under 256 MiB) from bit start_bit on into
+ * d_text[0, text_capacity).  d_history: the 32768 bytes of text before start_bit (device memory), or NULL at a member's
+ * start.  part_bytes: a multiple of 8, at least 64; 0 = 32768.  The span ends at the member's end, at the last block
+ * boundary its bytes hold, or (BC_GUNZIP_OUTPUT_FULL) where the text stops fitting: then nothing is written and the
+ * caller comes back with the span cut at end_bit.  Runs on hip_stream and waits for it.  BC_OK whatever the stream is
+ * like (the result says); a damaged stream never reads or writes outside the buffers. */
+int bc_gunzip_span_device(int device_id, void *hip_stream, const void *d_src, uint64_t src_bytes, uint64_t start_bit,
+                          const void *d_history, void *d_text, uint64_t text_capacity, uint32_t part_bytes,
+                          bc_gunzip_result *result);
+/* segments inflated that way for this engine since it was created (by bc_fastq_count*) */
+int bc_engine_gz_segments_inflated(const bc_engine *e, uint64_t *n);
+
 /* ---- synthetic workloads (bench + full-size parity) -------------------------------------- */
 
 typedef struct bc_synth_params {

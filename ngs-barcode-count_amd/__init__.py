@@ -252,6 +252,12 @@ class Engine:
         _check(self._lib, self._lib.bc_engine_gz_blocks_inflated(self._e, C.byref(n)))
         return n.value
 
+    def gz_segments_inflated(self):
+        """segments of ordinary gzip streams inflated on the device for this engine since it was created (BC_GZ_DEVICE=all)"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_gz_segments_inflated(self._e, C.byref(n)))
+        return n.value
+
     def sclk_mhz(self):
         """shader clock right now (0.3 ms probe kernel)"""
         v = C.c_double()

@@ -29,6 +29,12 @@ class BgzfBlock(C.Structure):  # bc_bgzf_block
                 ("crc32", C.c_uint32)]
 
 
+class GunzipResult(C.Structure):  # bc_gunzip_result
+    _fields_ = [("status", C.c_uint32), ("detail", C.c_uint32), ("text_bytes", C.c_uint64), ("end_bit", C.c_uint64),
+                ("member_end", C.c_uint32), ("segments", C.c_uint32), ("rejected", C.c_uint32), ("crc32", C.c_uint32)]
+
+
+BC_GUNZIP_OK, BC_GUNZIP_OUTPUT_FULL, BC_GUNZIP_BAD_STREAM = 0, 1, 2
 INFLATE_STATUS = ["ok", "bad block type", "bad code lengths", "invalid symbol or distance", "input overrun",
                   "output overrun", "ISIZE mismatch", "CRC32 mismatch"]
 
@@ -140,6 +146,8 @@ ENGINE_API = {
     "bc_fastq_gz_record_start": (_int, [_cp, _u64, C.POINTER(C.c_uint64)]),
     "bc_bgzf_inflate_device": (_int, [_int, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "bc_engine_gz_blocks_inflated": (_int, [_vp, C.POINTER(C.c_uint64)]),
+    "bc_gunzip_span_device": (_int, [_int, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u32, C.POINTER(GunzipResult)]),
+    "bc_engine_gz_segments_inflated": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_comm_sum_u64": (_int, [_vp, C.POINTER(C.c_uint64), _int, _int]),
     "bc_synth_create": (_vp, [_vp, C.POINTER(SynthParams)]),
     "bc_synth_destroy": (None, [_vp]),

@@ -48,4 +48,11 @@ const char* bgzf_status_name(uint32_t status);
 // BGZF blocks inflated on the device for this engine (bc_engine.hip)
 void engine_add_gz_blocks(bc_engine* e, uint64_t n);
 
+// bc_gunzip_span_device (bc_gunzip.hip), for the ingest.  history_bytes: how many of the 32 KiB at d_history are the
+// member's own text (the last ones): a distance that reaches before them is kInfBadSymbol.
+int gunzip_span(int device_id, void* hip_stream, const void* d_src, uint64_t src_bytes, uint64_t start_bit, const void* d_history,
+                uint32_t history_bytes, void* d_text, uint64_t text_capacity, uint32_t part_bytes, bc_gunzip_result* res);
+// segments of ordinary gzip streams inflated on the device for this engine (bc_engine.hip)
+void engine_add_gz_segments(bc_engine* e, uint64_t n);
+
 }  // namespace bc

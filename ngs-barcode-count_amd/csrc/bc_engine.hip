@@ -2223,6 +2223,11 @@ int bc_engine_gz_blocks_inflated(const bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
+int bc_engine_gz_segments_inflated(const bc_engine* e, uint64_t* n) {
+  *n = e->gz_segments;
+  return BC_OK;
+}
+
 int bc_engine_sclk_mhz(bc_engine* e, double* mhz) {
   *mhz = 0.0;
   HIP_TRY(hipSetDevice(e->device));
@@ -2540,4 +2545,5 @@ int bc_synth_make_set(uint64_t seed, uint32_t n, uint32_t k, uint32_t min_dist, 
 // the ingest path's count of BGZF blocks inflated for this engine (bc_bgzf.hpp)
 namespace bc {
 void engine_add_gz_blocks(bc_engine* e, uint64_t n) { e->gz_blocks += n; }
+void engine_add_gz_segments(bc_engine* e, uint64_t n) { e->gz_segments += n; }
 }  // namespace bc

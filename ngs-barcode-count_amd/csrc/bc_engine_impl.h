@@ -88,6 +88,7 @@ struct bc_engine {
   uint64_t log_cap = 0;              // entries allocated in d_log / d_grouped
   uint32_t* d_log = nullptr;
   uint32_t* d_grouped = nullptr;
+  uint64_t gz_segments = 0;          // segments of ordinary gzip streams inflated on the device (bc_engine_gz_segments_inflated)
   uint64_t gz_blocks = 0;            // BGZF blocks inflated on the device for this engine (bc_engine_gz_blocks_inflated)
   uint64_t log_folds = 0;            // folds run since the engine was created (bc_engine_count_log_folds)
   uint32_t* d_fold_meta = nullptr;   // [cnt | start | cursor | item_off], kFoldMaxBuckets + 1 words each

@@ -173,6 +173,142 @@ BC_HD int inflate_symbol(uint64_t buf, const uint16_t* tab, uint32_t tab_bits, c
   return -1;
 }
 
+// ---- the pieces inflate_member and the span inflater (bc_gunzip.h) share: the bit reader and the block header ----
+
+// at least 32 valid bits afterwards (zero bits past the payload's end): the most one step takes is a distance code with
+// its extra bits, 28
+BC_HD void inflate_refill(InflateBits& r, const BC_GLOBAL uint8_t* src, uint32_t src_len, InflateTables& T, uint32_t self_lane) {
+  (void)self_lane;
+  if (r.cnt <= 32u) {
+    if (r.in_pos - r.win_base >= kInfWindow) {
+      BC_INF_WAVE_SYNC();
+      BC_INF_LANES(lane) {
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < 4u; ++k) {
+          const uint32_t at = r.in_pos + 4u * lane + k;
+          if (at < src_len) w |= (uint32_t)src[at] << (8u * k);
+        }
+        T.win[lane] = w;
+      }
+      BC_INF_WAVE_SYNC();
+      r.win_base = r.in_pos;
+    }
+    r.buf |= (uint64_t)T.win[(r.in_pos - r.win_base) >> 2] << r.cnt;
+    r.cnt += 32u;
+    r.in_pos += 4u;
+  }
+}
+BC_HD void inflate_drop(InflateBits& r, uint32_t n) {
+  r.buf >>= n;
+  r.cnt -= n;
+}
+// payload bytes of which at least one bit has been consumed > src_len
+BC_HD bool inflate_overrun(const InflateBits& r, uint32_t src_len) { return r.in_pos - (r.cnt >> 3) > src_len; }
+
+// The code of a block of type 1 (fixed) or 2 (dynamic: its header is read off `r`): the code lengths, both decoding
+// tables and the checks zlib applies to them.  kInfOk, or the status the block ends the stream with.
+BC_HD uint32_t inflate_block_tables(InflateBits& r, const BC_GLOBAL uint8_t* src, uint32_t src_len, uint32_t type, InflateTables& T,
+                                    uint32_t self_lane) {
+#define BC_INF_REFILL() inflate_refill(r, src, src_len, T, self_lane)
+#define BC_INF_DROP(n) inflate_drop(r, (n))
+#define BC_INF_OVERRUN() inflate_overrun(r, src_len)
+  uint32_t n_lit = 288, n_dist = 32;
+  if (type == 1u) {
+    for (uint32_t base = 0; base < 320u; base += 64u) {
+      BC_INF_LANES(lane) {
+        const uint32_t s = base + lane;
+        T.lens[s] = (uint8_t)(s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : s < 288u ? 8u : 5u);
+      }
+    }
+  } else {
+    BC_INF_REFILL();
+    n_lit = ((uint32_t)r.buf & 31u) + 257u;
+    n_dist = (((uint32_t)r.buf >> 5) & 31u) + 1u;
+    const uint32_t n_cl = (((uint32_t)r.buf >> 10) & 15u) + 4u;
+    BC_INF_DROP(14u);
+    if (n_lit > 286u || n_dist > 30u) return kInfBadCodeLengths;
+    BC_INF_WAVE_SYNC();
+    BC_INF_LANES(lane) {
+      if (lane < 19u) T.lens[320u + lane] = 0;
+    }
+    BC_INF_WAVE_SYNC();
+    constexpr uint8_t kOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+#pragma unroll
+    for (uint32_t i = 0; i < 19u; ++i) {
+      if (i < n_cl) {
+        BC_INF_REFILL();
+        T.lens[320u + kOrder[i]] = (uint8_t)((uint32_t)r.buf & 7u);
+        BC_INF_DROP(3u);
+      }
+    }
+    if (BC_INF_OVERRUN()) return kInfInputOverrun;
+    if (inflate_build(T.lens + 320, 19u, T.dist, kInfClBits, T.dcount, T.dsym, T.offs, self_lane) != 0) return kInfBadCodeLengths;
+    const uint32_t n_all = n_lit + n_dist;
+    uint32_t idx = 0;
+    while (idx < n_all) {  // (every turn adds at least one length)
+      BC_INF_REFILL();
+      uint32_t cl = 0;
+      const int sym = inflate_symbol(r.buf, T.dist, kInfClBits, T.dcount, T.dsym, &cl);
+      if (sym < 0) return kInfBadSymbol;
+      BC_INF_DROP(cl);
+      uint32_t value = (uint32_t)sym, rep = 1;
+      if (sym == 16) {
+        if (idx == 0) return kInfBadCodeLengths;
+        value = T.lens[idx - 1];
+        rep = 3u + ((uint32_t)r.buf & 3u);
+        BC_INF_DROP(2u);
+      } else if (sym == 17) {
+        value = 0;
+        rep = 3u + ((uint32_t)r.buf & 7u);
+        BC_INF_DROP(3u);
+      } else if (sym == 18) {
+        value = 0;
+        rep = 11u + ((uint32_t)r.buf & 127u);
+        BC_INF_DROP(7u);
+      }
+      if (BC_INF_OVERRUN()) return kInfInputOverrun;
+      if (rep > n_all - idx) return kInfBadCodeLengths;
+      for (uint32_t k = 0; k < rep; ++k) T.lens[idx + k] = (uint8_t)value;  // (the same store on every lane)
+      idx += rep;
+    }
+    BC_INF_WAVE_SYNC();
+    if (T.lens[256] == 0) return kInfBadCodeLengths;
+  }
+  const int left_lit = inflate_build(T.lens, n_lit, T.lit, kInfLitBits, T.lcount, T.lsym, T.offs, self_lane);
+  const int left_dist = inflate_build(T.lens + n_lit, n_dist, T.dist, kInfDistBits, T.dcount, T.dsym, T.offs, self_lane);
+  if (left_lit < 0 || left_dist < 0) return kInfBadCodeLengths;
+  if (type == 2u) {
+    // as zlib: an incomplete literal/length code is refused; an incomplete distance code only passes when it has no
+    // code at all (a block of literals) or a single code of one bit
+    if (left_lit > 0) return kInfBadCodeLengths;
+    uint32_t n_codes = 0;
+    for (uint32_t l = 1; l <= 15u; ++l) n_codes += T.dcount[l];
+    if (left_dist > 0 && !(n_codes == 0u || (n_codes == 1u && T.dcount[1] == 1u))) return kInfBadCodeLengths;
+  }
+  return kInfOk;
+#undef BC_INF_REFILL
+#undef BC_INF_DROP
+#undef BC_INF_OVERRUN
+}
+
+// the length of a match from its symbol (257 .. 285) and the extra bits on `r`
+BC_HD uint32_t inflate_match_length(InflateBits& r, uint32_t sym) {
+  if (sym < 265u) return sym - 254u;
+  if (sym == 285u) return 258u;
+  const uint32_t eb = (sym - 261u) >> 2;
+  const uint32_t len = 3u + ((4u + ((sym - 265u) & 3u)) << eb) + ((uint32_t)r.buf & ((1u << eb) - 1u));
+  inflate_drop(r, eb);
+  return len;
+}
+// the distance of a match from its symbol (0 .. 29) and the extra bits on `r`
+BC_HD uint32_t inflate_match_distance(InflateBits& r, uint32_t ds) {
+  if (ds < 4u) return ds + 1u;
+  const uint32_t eb = (ds >> 1) - 1u;
+  const uint32_t dist = 1u + ((2u + (ds & 1u)) << eb) + ((uint32_t)r.buf & ((1u << eb) - 1u));
+  inflate_drop(r, eb);
+  return dist;
+}
+
 // Inflates the deflate stream src[0, src_len) into out[0, isize) and checks ISIZE and CRC32.  Called by all 64 lanes of
 // a wave with the same arguments (self_lane = the lane's number; the host passes 0 and plays every lane in turn).
 BC_HD uint32_t inflate_member(const BC_GLOBAL uint8_t* src, uint32_t src_len, BC_GLOBAL uint8_t* out, uint32_t isize,
@@ -182,36 +318,9 @@ BC_HD uint32_t inflate_member(const BC_GLOBAL uint8_t* src, uint32_t src_len, BC
   r.win_base = 0u - kInfWindow;
   uint32_t pos = 0;  // bytes of output made
 
-  // at least 32 valid bits afterwards (zero bits past the payload's end): the most one step takes is a distance code
-  // with its extra bits, 28
-#define BC_INF_REFILL()                                                            \
-  do {                                                                             \
-    if (r.cnt <= 32u) {                                                            \
-      if (r.in_pos - r.win_base >= kInfWindow) {                                   \
-        BC_INF_WAVE_SYNC();                                                        \
-        BC_INF_LANES(lane) {                                                       \
-          uint32_t w = 0;                                                          \
-          for (uint32_t k = 0; k < 4u; ++k) {                                      \
-            const uint32_t at = r.in_pos + 4u * lane + k;                          \
-            if (at < src_len) w |= (uint32_t)src[at] << (8u * k);                  \
-          }                                                                        \
-          T.win[lane] = w;                                                         \
-        }                                                                          \
-        BC_INF_WAVE_SYNC();                                                        \
-        r.win_base = r.in_pos;                                                     \
-      }                                                                            \
-      r.buf |= (uint64_t)T.win[(r.in_pos - r.win_base) >> 2] << r.cnt;             \
-      r.cnt += 32u;                                                                \
-      r.in_pos += 4u;                                                              \
-    }                                                                              \
-  } while (0)
-#define BC_INF_DROP(n) \
-  do {                 \
-    r.buf >>= (n);     \
-    r.cnt -= (n);      \
-  } while (0)
-  // payload bytes of which at least one bit has been consumed
-#define BC_INF_OVERRUN() (r.in_pos - (r.cnt >> 3) > src_len)
+#define BC_INF_REFILL() inflate_refill(r, src, src_len, T, self_lane)
+#define BC_INF_DROP(n) inflate_drop(r, (n))
+#define BC_INF_OVERRUN() inflate_overrun(r, src_len)
 
   uint32_t last = 0;
   do {
@@ -244,78 +353,9 @@ BC_HD uint32_t inflate_member(const BC_GLOBAL uint8_t* src, uint32_t src_len, BC
       r.win_base = r.in_pos - kInfWindow;
       continue;
     }
-    uint32_t n_lit = 288, n_dist = 32;
-    if (type == 1u) {
-      for (uint32_t base = 0; base < 320u; base += 64u) {
-        BC_INF_LANES(lane) {
-          const uint32_t s = base + lane;
-          T.lens[s] = (uint8_t)(s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : s < 288u ? 8u : 5u);
-        }
-      }
-    } else {
-      BC_INF_REFILL();
-      n_lit = ((uint32_t)r.buf & 31u) + 257u;
-      n_dist = (((uint32_t)r.buf >> 5) & 31u) + 1u;
-      const uint32_t n_cl = (((uint32_t)r.buf >> 10) & 15u) + 4u;
-      BC_INF_DROP(14u);
-      if (n_lit > 286u || n_dist > 30u) return kInfBadCodeLengths;
-      BC_INF_WAVE_SYNC();
-      BC_INF_LANES(lane) {
-        if (lane < 19u) T.lens[320u + lane] = 0;
-      }
-      BC_INF_WAVE_SYNC();
-      constexpr uint8_t kOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-#pragma unroll
-      for (uint32_t i = 0; i < 19u; ++i) {
-        if (i < n_cl) {
-          BC_INF_REFILL();
-          T.lens[320u + kOrder[i]] = (uint8_t)((uint32_t)r.buf & 7u);
-          BC_INF_DROP(3u);
-        }
-      }
-      if (BC_INF_OVERRUN()) return kInfInputOverrun;
-      if (inflate_build(T.lens + 320, 19u, T.dist, kInfClBits, T.dcount, T.dsym, T.offs, self_lane) != 0) return kInfBadCodeLengths;
-      const uint32_t n_all = n_lit + n_dist;
-      uint32_t idx = 0;
-      while (idx < n_all) {  // (every turn adds at least one length)
-        BC_INF_REFILL();
-        uint32_t cl = 0;
-        const int sym = inflate_symbol(r.buf, T.dist, kInfClBits, T.dcount, T.dsym, &cl);
-        if (sym < 0) return kInfBadSymbol;
-        BC_INF_DROP(cl);
-        uint32_t value = (uint32_t)sym, rep = 1;
-        if (sym == 16) {
-          if (idx == 0) return kInfBadCodeLengths;
-          value = T.lens[idx - 1];
-          rep = 3u + ((uint32_t)r.buf & 3u);
-          BC_INF_DROP(2u);
-        } else if (sym == 17) {
-          value = 0;
-          rep = 3u + ((uint32_t)r.buf & 7u);
-          BC_INF_DROP(3u);
-        } else if (sym == 18) {
-          value = 0;
-          rep = 11u + ((uint32_t)r.buf & 127u);
-          BC_INF_DROP(7u);
-        }
-        if (BC_INF_OVERRUN()) return kInfInputOverrun;
-        if (rep > n_all - idx) return kInfBadCodeLengths;
-        for (uint32_t k = 0; k < rep; ++k) T.lens[idx + k] = (uint8_t)value;  // (the same store on every lane)
-        idx += rep;
-      }
-      BC_INF_WAVE_SYNC();
-      if (T.lens[256] == 0) return kInfBadCodeLengths;
-    }
-    const int left_lit = inflate_build(T.lens, n_lit, T.lit, kInfLitBits, T.lcount, T.lsym, T.offs, self_lane);
-    const int left_dist = inflate_build(T.lens + n_lit, n_dist, T.dist, kInfDistBits, T.dcount, T.dsym, T.offs, self_lane);
-    if (left_lit < 0 || left_dist < 0) return kInfBadCodeLengths;
-    if (type == 2u) {
-      // as zlib: an incomplete literal/length code is refused; an incomplete distance code only passes when it has no
-      // code at all (a block of literals) or a single code of one bit
-      if (left_lit > 0) return kInfBadCodeLengths;
-      uint32_t n_codes = 0;
-      for (uint32_t l = 1; l <= 15u; ++l) n_codes += T.dcount[l];
-      if (left_dist > 0 && !(n_codes == 0u || (n_codes == 1u && T.dcount[1] == 1u))) return kInfBadCodeLengths;
+    {
+      const uint32_t st = inflate_block_tables(r, src, src_len, type, T, self_lane);
+      if (st != kInfOk) return st;
     }
     for (;;) {  // (every turn consumes at least one bit: bounded by the overrun check)
       BC_INF_REFILL();
@@ -334,28 +374,12 @@ BC_HD uint32_t inflate_member(const BC_GLOBAL uint8_t* src, uint32_t src_len, BC
       }
       if (sym == 256) break;
       if (sym > 285) return kInfBadSymbol;
-      uint32_t len;
-      if (sym < 265) {
-        len = (uint32_t)sym - 254u;
-      } else if (sym == 285) {
-        len = 258u;
-      } else {
-        const uint32_t eb = ((uint32_t)sym - 261u) >> 2;
-        len = 3u + ((4u + (((uint32_t)sym - 265u) & 3u)) << eb) + ((uint32_t)r.buf & ((1u << eb) - 1u));
-        BC_INF_DROP(eb);
-      }
+      const uint32_t len = inflate_match_length(r, (uint32_t)sym);
       BC_INF_REFILL();
       const int ds = inflate_symbol(r.buf, T.dist, kInfDistBits, T.dcount, T.dsym, &cl);
       if (ds < 0 || ds > 29) return kInfBadSymbol;
       BC_INF_DROP(cl);
-      uint32_t dist;
-      if (ds < 4) {
-        dist = (uint32_t)ds + 1u;
-      } else {
-        const uint32_t eb = ((uint32_t)ds >> 1) - 1u;
-        dist = 1u + ((2u + ((uint32_t)ds & 1u)) << eb) + ((uint32_t)r.buf & ((1u << eb) - 1u));
-        BC_INF_DROP(eb);
-      }
+      const uint32_t dist = inflate_match_distance(r, (uint32_t)ds);
       if (BC_INF_OVERRUN()) return kInfInputOverrun;
       if (dist > pos) return kInfBadSymbol;
       if (len > isize - pos) return kInfOutputOverrun;

@@ -6,7 +6,8 @@
 // mutex-guarded VecDeque; here the host only MOVES bytes and the device does the framing:
 //
 //   host     a reader team pread()s the file (page cache -> pinned chunk buffers, several threads; zlib for .gz,
-//            unless the file is BGZF: then the compressed bytes travel and the device inflates them, bc_inflate.hip),
+//            unless the file is BGZF: then the compressed bytes travel and the device inflates them, bc_inflate.hip;
+//            with BC_GZ_DEVICE=all the same holds for an ordinary gzip stream, span by span, bc_gunzip.hip),
 //   PCIe     the raw text goes to the device as it is (hipMemcpyAsync on the ingest stream),
 //   device   newline scan (count, prefix sum, positions), record table (where each record's sequence and quality
 //            line start, how long they are), then a gather into the fixed-stride sequence / quality batch the match
@@ -322,6 +323,14 @@ struct Ingest {
   DevState* d_state = nullptr;
   bool gz = false;
   bool bgzf = false;               // this call inflates on the device
+  // ordinary gzip on the device (BC_GZ_DEVICE=all): the producer thread inflates span after span into the slot's text
+  // buffer on a stream of its own, and copies the overlap itself (a span's history is the 32 KiB in front of its text)
+  bool gzdev = false;
+  hipStream_t st_gz = nullptr;
+  uint8_t* gz_pin = nullptr;       // pinned: the compressed bytes not yet inflated, from the current block boundary on
+  uint8_t* d_gz_comp = nullptr;
+  size_t comp_cap = 0;
+  std::vector<uint8_t> gz_head;    // the stream's first text, for the first-record check
   size_t blk_cap = 0;              // blocks per chunk the BGZF buffers hold (0: not allocated yet)
   const std::vector<BgzfMember>* members = nullptr;
   std::string path;
@@ -340,6 +349,19 @@ struct Ingest {
       HIP_TRY(hipMalloc((void**)&s.d_blk_status, cap * sizeof(uint32_t)));
     }
     blk_cap = cap;
+    return BC_OK;
+  }
+
+  int alloc_gzdev(size_t cap) {
+    if (comp_cap >= cap) return BC_OK;
+    if (gz_pin) (void)hipHostFree(gz_pin);
+    if (d_gz_comp) (void)hipFree(d_gz_comp);
+    gz_pin = d_gz_comp = nullptr;
+    comp_cap = 0;
+    if (!st_gz) HIP_TRY(hipStreamCreateWithFlags(&st_gz, hipStreamNonBlocking));
+    HIP_TRY(hipHostMalloc((void**)&gz_pin, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void**)&d_gz_comp, cap + 64));
+    comp_cap = cap;
     return BC_OK;
   }
 
@@ -386,6 +408,9 @@ struct Ingest {
         if (ev) (void)hipEventDestroy(ev);
     }
     if (d_state) (void)hipFree(d_state);
+    if (gz_pin) (void)hipHostFree(gz_pin);
+    if (d_gz_comp) (void)hipFree(d_gz_comp);
+    if (st_gz) (void)hipStreamDestroy(st_gz);
     if (st) (void)hipStreamDestroy(st);
   }
 
@@ -393,7 +418,9 @@ struct Ingest {
   int frame(int b, const Slot* prev) {
     Slot& s = slot[b];
     HIP_TRY(hipStreamWaitEvent(st, s.consumed, 0));  // the batch arrays of this slot may still be read by a match kernel
-    if (!bgzf) {
+    if (gzdev) {
+      // (the text and the overlap in front of it are in place: the producer put them there and waited for them)
+    } else if (!bgzf) {
       HIP_TRY(hipMemcpyAsync(s.d_text + kOverlap, s.pin, s.len, hipMemcpyHostToDevice, st));
       HIP_TRY(hipEventRecord(s.uploaded, st));
     } else {
@@ -403,8 +430,9 @@ struct Ingest {
     s.ov = 0;
     if (prev) {
       s.ov = std::min(kOverlap, prev->ov + prev->len);
-      hipLaunchKernelGGL(ingest_overlap_kernel, dim3((uint32_t)((s.ov + 255) / 256)), dim3(256), 0, st,
-                         prev->d_text + kOverlap + prev->len, s.d_text + kOverlap, (uint32_t)s.ov);
+      if (!gzdev)
+        hipLaunchKernelGGL(ingest_overlap_kernel, dim3((uint32_t)((s.ov + 255) / 256)), dim3(256), 0, st,
+                           prev->d_text + kOverlap + prev->len, s.d_text + kOverlap, (uint32_t)s.ov);
     }
     const uint8_t* text = s.d_text + kOverlap - s.ov;  // 16-byte aligned: kOverlap and ov are multiples of 16 ...
     // ... unless the previous chunk was shorter than the overlap (only the file's first chunks can be): align down
@@ -655,6 +683,178 @@ long long gz_record_start_at_or_after(BgzfHostReader& hr, unsigned long long off
                                   hr.inflated, 64u << 10);
 }
 
+struct GzDevStats {
+  uint64_t spans = 0, segments = 0, rejected = 0, retries = 0;
+};
+
+// The gzip-device producer: compressed bytes from the file, member headers and trailers on the host, the deflate
+// stream between them span by span through the device (bc_gunzip.hip).  What it keeps between chunks: the compressed
+// bytes from the current block boundary on (pin[0, have), the boundary at bit `bit` of pin[0]) and the member's running
+// CRC and length.
+struct GzDevProducer {
+  int fd = -1, device = 0;
+  hipStream_t st = nullptr;
+  uint8_t* pin = nullptr;
+  uint8_t* d_comp = nullptr;
+  size_t comp_cap = 0, span_bytes = 0;
+  uint32_t part_bytes = 32768;
+  std::string path, error;
+  GzDevStats* stats = nullptr;
+  unsigned long long fpos = 0;      // next file byte to read
+  size_t have = 0;
+  uint32_t bit = 0;
+  bool file_end = false, in_member = false, any_member = false, stream_end = false;
+  unsigned long long member_off = 0, member_len = 0;
+  uint32_t member_crc = 0;
+
+  unsigned long long pin_off() const { return fpos - have; }  // file offset of pin[0]
+  int fail(const std::string& what, int code = BC_ERR_INVALID) {
+    error = "read error in " + path + ": gzip member at file offset " + std::to_string(member_off) + ": " + what;
+    return code;
+  }
+  // pin[0, want) from the file, as far as it goes
+  int top_up(size_t want) {
+    want = std::min(want, comp_cap);
+    while (have < want && !file_end) {
+      const ssize_t n = pread(fd, pin + have, want - have, (off_t)fpos);
+      if (n < 0) return fail("pread failed");
+      if (n == 0) file_end = true;
+      have += (size_t)n;
+      fpos += (unsigned long long)n;
+    }
+    return BC_OK;
+  }
+  void consume(size_t n) {
+    memmove(pin, pin + n, have - n);
+    have -= n;
+  }
+  // the member header at pin[0]: > 0 its length, 0: more bytes are needed, -1: no gzip member here, -2: refused
+  long header() const {
+    if (have < 10) return file_end ? -1 : 0;
+    if (pin[0] != 0x1F || pin[1] != 0x8B) return -1;
+    if (pin[2] != 8 || (pin[3] & 0xE0)) return -2;  // (not deflate, or reserved flags: a preset dictionary among them)
+    const uint32_t flg = pin[3];
+    size_t p = 10;
+    if (flg & 4) {  // FEXTRA
+      if (have < p + 2) return file_end ? -1 : 0;
+      p += 2 + ((size_t)pin[p] | ((size_t)pin[p + 1] << 8));
+    }
+    for (uint32_t f : {8u, 16u})  // FNAME, FCOMMENT
+      if (flg & f) {
+        const void* z = p < have ? memchr(pin + p, 0, have - p) : nullptr;
+        if (!z) return file_end ? -1 : 0;
+        p = (size_t)((const uint8_t*)z - pin) + 1;
+      }
+    if (flg & 2) p += 2;  // FHCRC
+    if (p > have) return file_end ? -1 : 0;
+    return (long)p;
+  }
+
+  // Fills d_text[0, cap) with the stream's next text (behind it: the text before, at least 32 KiB of it unless the
+  // stream is younger).  *last: the stream ends with this text; *patched: its unterminated last character became '\n'.
+  int fill(uint8_t* d_text, size_t cap, size_t* text, bool* last, bool* patched, std::vector<uint8_t>* head) {
+    size_t cur = 0, target = span_bytes;
+    *last = *patched = false;
+    while (!stream_end) {
+      if (!in_member) {
+        int rc = top_up(std::max<size_t>(target, 4096));
+        if (rc != BC_OK) return rc;
+        if (have == 0) {
+          stream_end = true;
+          break;
+        }
+        member_off = pin_off();
+        long hb = header();
+        if (hb == 0) {
+          if ((rc = top_up(comp_cap)) != BC_OK) return rc;
+          hb = header();
+        }
+        if (hb == -2) return fail("not deflate, or a header flag this program refuses", BC_ERR_UNSUPPORTED);
+        if (hb <= 0) {
+          if (!any_member) return fail("no gzip header");
+          stream_end = true;  // (what follows the last member is ignored, as zlib's gzread does)
+          break;
+        }
+        consume((size_t)hb);
+        in_member = any_member = true;
+        bit = 0;
+        member_len = 0;
+        member_crc = 0;
+      }
+      int rc = top_up(target);
+      if (rc != BC_OK) return rc;
+      size_t n = std::min(have, target);
+      bc_gunzip_result res;
+      for (int attempt = 0;; ++attempt) {
+        if (hipMemcpyAsync(d_comp, pin, n, hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload failed", BC_ERR_HIP);
+        const void* hist = member_len ? d_text + cur - 32768 : nullptr;  // (in front of d_text lies the overlap: 4 MiB)
+        const uint32_t hist_len = (uint32_t)std::min<unsigned long long>(member_len, 32768);  // the member's own text among them
+        if (gunzip_span(device, st, d_comp, n, bit, hist, hist_len, d_text + cur, cap - cur, part_bytes, &res) != BC_OK)
+          return fail("the device inflater failed", BC_ERR_HIP);
+        ++stats->spans;
+        stats->rejected += res.rejected;
+        if (res.status != BC_GUNZIP_OUTPUT_FULL || res.text_bytes == 0 || attempt) break;
+        n = (size_t)((res.end_bit + 7) / 8);  // the text does not fit: the span again, cut at the last boundary that does
+        ++stats->retries;
+      }
+      if (res.status == BC_GUNZIP_BAD_STREAM) return fail(bgzf_status_name(res.detail));
+      if (res.status == BC_GUNZIP_OUTPUT_FULL) {
+        if (cur > 0 && res.text_bytes == 0) break;  // the chunk is full: the next one starts with this block
+        // (a span cut at the boundary that fits measures as it did before the cut: it cannot be full again)
+        if (res.text_bytes) return fail("internal error: a span cut at the boundary that fits is reported full again", BC_ERR_STATE);
+        return fail("a single deflate block holds more text than the ingest's text buffer of " + std::to_string(cap) +
+                        " bytes: raise BC_INGEST_CHUNK, or read this file through zlib with BC_GZ_DEVICE=1",
+                    BC_ERR_UNSUPPORTED);
+      }
+      if (res.end_bit == bit && !res.member_end) {  // no whole block among the span's bytes
+        if (n >= have && file_end) return fail("the stream ends inside a deflate block");
+        if (n >= comp_cap)
+          return fail("a single deflate block is larger than the ingest's buffers: raise BC_INGEST_CHUNK, or read this file through "
+                      "zlib with BC_GZ_DEVICE=1", BC_ERR_UNSUPPORTED);
+        target = std::min(comp_cap, 2 * target);
+        continue;
+      }
+      target = span_bytes;
+      stats->segments += res.segments;
+      cur += (size_t)res.text_bytes;
+      member_crc = (uint32_t)crc32_combine(member_crc, res.crc32, (z_off_t)res.text_bytes);
+      member_len += res.text_bytes;
+      consume((size_t)(res.end_bit >> 3));
+      bit = (uint32_t)(res.end_bit & 7u);
+      if (res.member_end) {
+        if (bit) consume(1);
+        bit = 0;
+        if ((rc = top_up(std::max<size_t>(8, std::min(have, target)))) != BC_OK) return rc;
+        if (have < 8) return fail("the file ends before the member's trailer");
+        const uint32_t want_crc = (uint32_t)pin[0] | ((uint32_t)pin[1] << 8) | ((uint32_t)pin[2] << 16) | ((uint32_t)pin[3] << 24);
+        const uint32_t want_len = (uint32_t)pin[4] | ((uint32_t)pin[5] << 8) | ((uint32_t)pin[6] << 16) | ((uint32_t)pin[7] << 24);
+        if (want_crc != member_crc) return fail("CRC32 mismatch");
+        if (want_len != (uint32_t)member_len) return fail("ISIZE mismatch");
+        consume(8);
+        in_member = false;
+      }
+    }
+    if (head) {
+      head->resize(std::min<size_t>(cur, 1u << 20));
+      if (!head->empty() && hipMemcpyAsync(head->data(), d_text, head->size(), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail("reading the first text back failed", BC_ERR_HIP);
+    }
+    if (stream_end && cur) {  // the gz rule for an unterminated last character (see the caller)
+      uint8_t c = '\n';
+      if (hipMemcpyAsync(&c, d_text + cur - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail("reading the last character back failed", BC_ERR_HIP);
+      if (c != '\n') {
+        if (bgzf_patch_newline_launch(st, d_text, cur - 1) != (int)hipSuccess) return fail("patching the last character failed", BC_ERR_HIP);
+        *patched = true;
+      }
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("the device refused the gzip stage", BC_ERR_HIP);
+    *text = cur;
+    *last = stream_end;
+    return BC_OK;
+  }
+};
+
 }  // namespace
 
 static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard, uint32_t n_shards, uint64_t* total_reads,
@@ -733,26 +933,33 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   // every other one is a single zlib stream on the host.
   std::vector<BgzfMember> members;
   uint64_t inflated = 0;
-  bool bgzf = false;
+  // BC_GZ_DEVICE=all: the latter goes to the device as well, span by span (bc_gunzip.hip).
+  bool bgzf = false, gzdev = false;
   if (gz) {
     const char* ev = getenv("BC_GZ_DEVICE");
     std::string why;
     if (!(ev && ev[0] == '0' && !ev[1])) bgzf = bgzf_index(path, &members, &inflated, &why) == 0;
+    gzdev = !bgzf && ev && !strcmp(ev, "all");
   }
+  GzDevStats gzs;
   const bool verbose = [] {
     const char* ev = getenv("BC_INGEST_VERBOSE");
     return ev && ev[0] && !(ev[0] == '0' && !ev[1]);
   }();
   uint64_t total = 0, blocks_this_call = 0;
   auto say = [&](int code) {
-    if (verbose)
+    if (verbose && gzdev)
+      fprintf(stderr, "[bc ingest] %s: path gzip-device, shard %u/%u, %llu spans, %llu segments, %llu candidates rejected, %llu retries, "
+              "%llu records counted%s\n", path.c_str(), shard, n_shards, (unsigned long long)gzs.spans, (unsigned long long)gzs.segments,
+              (unsigned long long)gzs.rejected, (unsigned long long)gzs.retries, (unsigned long long)total, code == BC_OK ? "" : " (failed)");
+    else if (verbose)
       fprintf(stderr, "[bc ingest] %s: path %s, shard %u/%u, %llu BGZF blocks inflated on the device, %llu records counted%s\n",
               path.c_str(), bgzf ? "bgzf-device" : gz ? "gzread" : "plain", shard, n_shards, (unsigned long long)blocks_this_call,
               (unsigned long long)total, code == BC_OK ? "" : " (failed)");
   };
   Source src;
-  src.gz = gz && !bgzf;
-  if (bgzf) {
+  src.gz = gz && !bgzf && !gzdev;
+  if (bgzf || gzdev) {
     src.fd = open(path.c_str(), O_RDONLY);
   } else if (gz) {
     src.zf = gzopen(path.c_str(), "rb");  // multi-member aware (flate2 MultiGzDecoder, input.rs:63)
@@ -815,7 +1022,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   if (n_shards > 1 && !bgzf) {
     if (gz) {
       if (shard != 0) {
-        gzclose(src.zf);
+        if (src.gz) gzclose(src.zf); else close(src.fd);
         say(BC_OK);
         return BC_OK;
       }
@@ -841,7 +1048,12 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
                  : gz  ? (32u << 20)
                        : (size_t)std::min<unsigned long long>(128u << 20, ((src.size >> 20) + 1) << 20);
   if (const char* ev = getenv("BC_INGEST_CHUNK")) chunk = (size_t)std::max(4096L, atol(ev));
+  // (a deflate block's text has to fit the text buffer: zlib's blocks hold 16 Ki symbols, a few hundred KiB of FASTQ)
+  if (gzdev) chunk = std::max<size_t>(chunk, 1u << 20);
   chunk = (chunk + 15) & ~(size_t)15;
+  size_t gz_span = chunk / 8, gz_part = 32768;
+  if (const char* ev = getenv("BC_GZ_SPAN_BYTES")) gz_span = (size_t)std::min(128L << 20, std::max(1024L, atol(ev)));
+  if (const char* ev = getenv("BC_GZ_PART_BYTES")) gz_part = (size_t)std::min(1L << 20, std::max(64L, atol(ev))) & ~(size_t)7;
   // BGZF chunks are cut at block boundaries: text of at most `fill_cap` bytes, but always a whole block, so the
   // buffers hold at least the largest block there can be
   const size_t fill_cap = chunk;
@@ -873,6 +1085,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     }
     if (rc == BC_OK) rc = g_cached->alloc();
     if (rc == BC_OK && bgzf) rc = g_cached->alloc_bgzf();
+    if (rc == BC_OK && gzdev) rc = g_cached->alloc_gzdev(chunk + gz_span + 65536);
     if (rc != BC_OK) {
       g_cached->release();
       delete g_cached;
@@ -890,7 +1103,17 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     say(rc);
     return rc;
   }
+  if (gzdev && (rc = g_cached->alloc_gzdev(chunk + gz_span + 65536)) != BC_OK) {
+    g_cached->release();
+    delete g_cached;
+    g_cached = nullptr;
+    close(src.fd);
+    say(rc);
+    return rc;
+  }
   Ingest& in = *g_cached;
+  in.gzdev = gzdev;
+  in.gz_head.clear();
   in.engine = e;
   in.gz = gz;
   in.bgzf = bgzf;
@@ -907,6 +1130,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     sl.patch_at = -1;
   }
   auto finish = [&](int code) {
+    if (in.st_gz) (void)hipStreamSynchronize(in.st_gz);
     (void)hipStreamSynchronize(in.st);
     (void)bc_engine_sync(e);  // the match kernels read the batch arrays, which the next call reuses
     if (src.gz)
@@ -937,8 +1161,24 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   int filled_upto = 0;   // chunks [0, filled_upto) are in their slots
   int released_upto = kSlots;  // the producer may fill chunks [.., released_upto)
   bool read_error = false, stop = false;
+  std::string gz_error;  // what the gzip-device producer found wrong (it becomes the call's error)
+  int gz_error_code = BC_ERR_INVALID;
+  GzDevProducer gzp;
+  if (gzdev) {
+    gzp.fd = src.fd;
+    gzp.device = device;
+    gzp.st = in.st_gz;
+    gzp.pin = in.gz_pin;
+    gzp.d_comp = in.d_gz_comp;
+    gzp.comp_cap = in.comp_cap;
+    gzp.span_bytes = gz_span;
+    gzp.part_bytes = (uint32_t)gz_part;
+    gzp.path = path;
+    gzp.stats = &gzs;
+  }
   std::thread producer([&] {
     unsigned long long off = 0;
+    size_t prev_ov = 0, prev_len = 0;  // (gzip-device: the overlap of the chunk before, as frame() will work it out)
     for (int i = 0;; ++i) {
       {
         std::unique_lock<std::mutex> lk(mu);
@@ -946,6 +1186,48 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
         if (stop) return;
       }
       Slot& s = in.slot[i % kSlots];
+      if (gzdev) {
+        // everything that reads this slot's text (its last chunk's framing and gather, the next chunk's overlap copy)
+        // was enqueued before the slot was released
+        bool bad = hipSetDevice(device) != hipSuccess || hipStreamSynchronize(in.st) != hipSuccess;
+        const size_t ov = i > 0 ? std::min(kOverlap, prev_ov + prev_len) : 0;
+        if (!bad && ov) {
+          const Slot& prev = in.slot[(i - 1) % kSlots];
+          hipLaunchKernelGGL(ingest_overlap_kernel, dim3((uint32_t)((ov + 255) / 256)), dim3(256), 0, in.st_gz,
+                             prev.d_text + kOverlap + prev_len, s.d_text + kOverlap, (uint32_t)ov);
+          bad = hipGetLastError() != hipSuccess;
+        }
+        size_t text = 0;
+        bool last = true, patched = false;
+        if (!bad) {
+          const int grc = gzp.fill(s.d_text + kOverlap, in.chunk, &text, &last, &patched, i == 0 ? &in.gz_head : nullptr);
+          if (grc != BC_OK) {
+            bad = true;
+            gz_error_code = grc;
+          }
+        } else {
+          gzp.error = "read error in " + path + ": the device refused the gzip stage";
+          gz_error_code = BC_ERR_HIP;
+        }
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          if (bad) {
+            read_error = true;
+            gz_error = gzp.error;
+          }
+          s.len = bad ? 0 : text;
+          s.patch_at = patched ? (long long)text - 1 : -1;
+          s.file_off = off;
+          s.eof = bad || last;
+          filled_upto = i + 1;
+        }
+        cv.notify_all();
+        if (bad || last) return;
+        off += text;
+        prev_ov = ov;
+        prev_len = text;
+        continue;
+      }
       (void)hipEventSynchronize(s.uploaded);  // the slot's previous text has left for the device
       if (bgzf) {
         // the next run of blocks whose text fits the chunk (at least one block), their bytes read as one span
@@ -1019,8 +1301,8 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
       std::unique_lock<std::mutex> lk(mu);
       cv.wait(lk, [&] { return filled_upto > i; });
       if (read_error) {
-        set_error("read error in " + path);
-        rc = BC_ERR_INVALID;
+        set_error(gz_error.empty() ? "read error in " + path : gz_error);
+        rc = gz_error.empty() ? BC_ERR_INVALID : gz_error_code;
       }
     }
     if (rc != BC_OK) break;
@@ -1042,8 +1324,8 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
           }
           if (head.size() > s.len) head.resize(s.len);
         }
-        const char* t = in.bgzf ? (const char*)head.data() : (const char*)s.pin;
-        const size_t tlen = in.bgzf ? head.size() : s.len;  // the text the check may look at
+        const char* t = in.bgzf ? (const char*)head.data() : in.gzdev ? (const char*)in.gz_head.data() : (const char*)s.pin;
+        const size_t tlen = in.bgzf ? head.size() : in.gzdev ? in.gz_head.size() : s.len;  // the text the check may look at
         const char* e1 = tlen ? (const char*)memchr(t, '\n', tlen) : nullptr;
         const char* e2 = e1 ? (const char*)memchr(e1 + 1, '\n', tlen - (size_t)(e1 + 1 - t)) : nullptr;
         // (a file of fewer than four whole lines never posts a record, so the reference never looks at it)
@@ -1064,7 +1346,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
         test = false;
         if (rc != BC_OK) break;
       }
-      if (in.bgzf) {
+      if (in.bgzf || in.gzdev) {
         // the unterminated last character of a gz stream becomes the missing newline (see below): on the device, after
         // the inflate kernel
         if (s.patch_at >= 0) {
@@ -1134,6 +1416,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   }
   cv.notify_all();
   producer.join();
+  if (gzdev) engine_add_gz_segments(e, gzs.segments);
   if (rc != BC_OK) return finish(rc);
 
   // what is left after the last whole record: fewer than four complete lines (+ possibly a last line without '\n')
