@@ -704,6 +704,7 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
 #ifdef BC_EXPERIMENT
   if (const char* pm = getenv("BC_PIPE")) e->pipe = atoi(pm) != 0;
 #endif
+  e->qshare = qual_region_shared();
   HIP_TRY(hipMalloc((void**)&e->d_plan, sizeof(DevPlan)));
   HIP_TRY(hipMemcpy(e->d_plan, &P, sizeof(DevPlan), hipMemcpyHostToDevice));
   for (uint32_t g = 0; g < P.n_groups; ++g) {
@@ -907,9 +908,11 @@ template <int NW, int NWW>
 static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
                         uint32_t read_len, uint32_t nd, uint64_t n_reads, uint64_t trace_off, const MatchShape& s) {
   // log mode (bc_fold.h): the batch goes through in chunks of at most log_chunk reads, each matched into the log and
-  // folded before the next one overwrites it.  (The hot-counter cache keeps its LDS either way: the same code object.)
+  // folded before the next one overwrites it.  (The same code object with the hot-counter cache on or off: the kernel
+  // lays out its LDS from the flag, so a launch without the cache does not ask for its bytes.)
   const bool use_log = log_mode_for(e, n_reads);
   const bool hot_on = !use_log || e->log_hot;
+  const uint32_t lds = hot_on ? s.lds : s.lds_cold, lds_jit = hot_on ? s.lds_jit : s.lds_jit_cold;
   // In log mode the kernel reads and writes only the reads, the log and the outcome counters -- unless the hot-counter
   // cache flushes to the table or the plan's search queue adds to it directly (neither touches the bit map): what a
   // reset owes can then wait for the fold (owed_plan).  Everyone else settles first.
@@ -930,13 +933,14 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   }
   auto kern = match_count_kernel<NW, NWW>;
   if (s.lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
-  // persistent grid: as many workgroups as the chip holds at once (or fewer for a small batch)
+  // persistent grid: as many workgroups as the chip holds at once (or fewer for a small batch), at the LDS this launch
+  // asks for
   int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kTPB, s.lds));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kTPB, lds));
   if (per_cu < 1) per_cu = 1;
   const uint64_t resident = (uint64_t)per_cu * e->n_cus;
   const uint64_t blocks = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, resident);
-  uint64_t blocks_jit = blocks;
+  uint64_t blocks_jit = blocks, resident_jit = resident;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (e->timing) {
     HIP_TRY(hipEventCreate(&e0));
@@ -947,8 +951,9 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   e->reads_seen += n_reads;
   if (NW <= 8 && NWW <= 4 && e->jit_mode != 0) {  // reads up to 256 bases; longer ones stay on the generic kernel
     int per_cu_jit = 1;
-    jit_fn = e->jit.function(e->h.plan, e->device, e->jit_mode, e->reads_seen, s, &per_cu_jit);
-    if (jit_fn) blocks_jit = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, (uint64_t)per_cu_jit * e->n_cus);
+    jit_fn = e->jit.function(e->h.plan, e->device, e->jit_mode, e->reads_seen, s, hot_on, &per_cu_jit);
+    resident_jit = (uint64_t)per_cu_jit * e->n_cus;
+    if (jit_fn) blocks_jit = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, resident_jit);
   }
   if (use_log) {
     const int rc = ensure_log(e, std::min<uint64_t>(n_reads, e->log_chunk));
@@ -989,10 +994,10 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
       void* args[] = {&a_seq, &a_qual, &a_lens, &a_qlens, &stride, &read_len, &nd, &a_n, &a_region, &e->d_table, &e->d_bits, &e->d_slots,
                       &e->d_vals, &a_smask, &e->d_counters, &a_to, &a_ti, &a_flags, &a_log};
       const uint64_t grid = std::min<uint64_t>(blocks_jit, (n_c + kTPB - 1) / kTPB);
-      HIP_TRY(hipModuleLaunchKernel(jit_fn, (uint32_t)grid, 1, 1, kTPB, 1, 1, s.lds_jit, e->stream, args, nullptr));
+      HIP_TRY(hipModuleLaunchKernel(jit_fn, (uint32_t)grid, 1, 1, kTPB, 1, 1, lds_jit, e->stream, args, nullptr));
     } else {
       const uint64_t grid = std::min<uint64_t>(blocks, (n_c + kTPB - 1) / kTPB);
-      hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(kTPB), s.lds, e->stream, e->d_plan, a_seq, a_qual, a_lens, a_qlens, stride, read_len,
+      hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual, a_lens, a_qlens, stride, read_len,
                          nd, a_n, s.region, e->d_table, e->d_bits, e->d_slots, e->d_vals, e->n_slots ? e->n_slots - 1 : 0, e->d_counters,
                          a_to, a_ti, flags, a_log);
     }
@@ -1014,6 +1019,10 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   }
   e->last_kernel = std::string(jit_fn ? "bc_jit_match_count<" : "match_count_kernel<") +
                    std::to_string(jit_fn ? s.jit.NW : NW) + "," + std::to_string(jit_fn ? s.jit.NWW : NWW) + ">";
+  e->last_key = jit_fn ? s.key : 0;
+  e->last_lds = jit_fn ? lds_jit : lds;
+  e->last_grid = (uint32_t)std::min<uint64_t>(jit_fn ? blocks_jit : blocks, (std::min<uint64_t>(chunk, n_reads) + kTPB - 1) / kTPB);
+  e->last_resident = (uint32_t)(jit_fn ? resident_jit : resident);
   if (e->timing) {
     HIP_TRY(hipEventRecord(e1, e->stream));
     e->events.emplace_back(e0, e1);
@@ -1153,7 +1162,7 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
   // plans or reads beyond the lane-per-read kernel's widths: the wave-per-read kernel (bc_long.h)
   if (e->long_only || maxlen > 320u) return launch_long(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads, trace_off);
   const MatchShape s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr,
-                                   e->lds_limit, e->pipe, e->lhash_mode);
+                                   e->lds_limit, e->pipe, e->qshare, e->lhash_mode);
   const int nww = s.jit.NWW;  // words of candidate offsets: the exact count; the instantiations round it up
 #define BC_LAUNCH(NW_, NWW_) \
   return launch_match<NW_, NWW_>(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, nd, n_reads, trace_off, s)
@@ -2212,6 +2221,16 @@ int bc_probe_atomic_rate(int device_id, void* d_table_u32, uint64_t entries, uin
 }
 
 const char* bc_engine_kernel_name(bc_engine* e) { return e ? e->last_kernel.c_str() : ""; }
+
+// test hook (not part of the documented ABI): the engine's last match launch -- the specialised kernel's shape key (0 when
+// the generic kernel ran), the dynamic LDS it asked for, its grid, and the workgroups the device holds of it at once
+int bc_internal_last_launch(const bc_engine* e, uint64_t* key, uint32_t* lds_bytes, uint32_t* grid, uint32_t* resident) {
+  *key = e->last_key;
+  *lds_bytes = e->last_lds;
+  *grid = e->last_grid;
+  *resident = e->last_resident;
+  return BC_OK;
+}
 
 int bc_engine_count_log_folds(const bc_engine* e, uint64_t* n) {
   *n = e->log_folds;

@@ -132,7 +132,13 @@ struct bc_engine {
   int jit_mode = 1;  // BC_JIT = 0: never | 1 (default): cache hit -> at once, else compiled in the background once 2^20
                      // reads have been seen | force (2): always, compiled synchronously | cached (3): cache hits only
   std::string last_kernel;
+  // the last match launch: the specialised kernel's shape key (0: the generic kernel ran), its dynamic LDS and its grid
+  // (bc_internal_last_launch)
+  uint64_t last_key = 0;
+  uint32_t last_lds = 0, last_grid = 0, last_resident = 0;
   bool pipe = true;   // software-pipelined tile fetch (BC_PIPE=0|1)
+  bool qshare = true; // the specialised kernel's tile regions: one per wave, shared by sequence and quality lines
+                      // (BC_QUAL_REGION=own|shared, read when the engine is created)
   int lhash_mode = 1; // LDS exact-match tables (PlanSetup::lhash_mode)
   // random-barcode mode: the hash set of (tuple, random barcode) keys
   unsigned long long* d_slots = nullptr;

@@ -32,6 +32,7 @@ inline int generic_nw(uint32_t maxlen) { return maxlen <= 128 ? 4 : (maxlen <= 2
 struct JitShape {
   int NW, NWW;  // exact words per read / words of candidate offsets of the batch shape
   bool lens, tables, trace;
+  bool qshare = false;        // quality filter with the pipelined fetch: sequence and quality lines share one LDS region
   uint32_t stride, read_len, region;
   bool conservative = false;  // last try after builds that needed scratch memory: the loop-based counting form
   int min_waves = 3;          // waves per SIMD the register allocation must leave room for (__launch_bounds__)
@@ -42,15 +43,20 @@ struct MatchShape {
   int generic_nw;                   // the generic instantiation's NW
   uint32_t region;                  // per-wave LDS region: 64 reads + the few bytes past them the lane code may touch
   uint32_t lds, lds_jit;            // dynamic LDS of the generic / specialised kernel
+  uint32_t lds_cold, lds_jit_cold;  // ... of a launch with the hot-counter cache off (the same where a plan has none)
   bool tables_generic, tables_jit;  // LDS exact-match tables
-  bool hot_generic, hot_jit;        // hot-counter cache (its LDS; log mode may still switch it off per launch)
+  bool hot_generic, hot_jit;        // hot-counter cache (log mode may still switch it off per launch: lds_cold)
   JitShape jit;
   int first_min_waves;              // waves per SIMD the specialised build tries first
   uint64_t key;                     // the engine's key for the specialised kernel of this shape
 };
-// table_entries: 0 for sparse plans; read_len: ignored with per-read lengths (lens); trace: per-read outcomes recorded
+// table_entries: 0 for sparse plans; read_len: ignored with per-read lengths (lens); trace: per-read outcomes recorded;
+// qshare: the specialised kernel of a plan with the quality filter and the pipelined fetch gets one tile region per
+// wave, not two
 MatchShape match_shape(const DevPlan& P, uint64_t table_entries, uint32_t stride, uint32_t read_len, bool lens, bool trace,
-                       uint32_t lds_limit, bool pipe, int lhash_mode);
+                       uint32_t lds_limit, bool pipe, bool qshare, int lhash_mode);
+// BC_QUAL_REGION=own|shared (default shared): what engines and the ahead-of-time build pass as qshare
+bool qual_region_shared();
 
 // scheme-specialised kernels of one engine, one per MatchShape::key; destruction joins the workers and unloads the
 // modules
@@ -63,7 +69,7 @@ struct JitKernels {
     std::string log;
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
-    int per_cu = 0;
+    int per_cu = 0, per_cu_cold = 0;  // workgroups per CU at lds_jit / lds_jit_cold
   };
   std::map<uint64_t, std::unique_ptr<Jit>> slots;
 
@@ -72,8 +78,10 @@ struct JitKernels {
   JitKernels& operator=(const JitKernels&) = delete;
   ~JitKernels();
   // The specialised kernel of one shape, if it can be had now (mode: BC_JIT as bc_engine::jit_mode reads it;
-  // reads_seen: reads submitted so far).  Returns nullptr while the generic kernel must do.
-  hipFunction_t function(const DevPlan& plan, int device, int mode, uint64_t reads_seen, const MatchShape& s, int* per_cu);
+  // reads_seen: reads submitted so far; hot_on: the launch uses the hot-counter cache, *per_cu: the workgroups a CU
+  // holds of such a launch).  Returns nullptr while the generic kernel must do.
+  hipFunction_t function(const DevPlan& plan, int device, int mode, uint64_t reads_seen, const MatchShape& s, bool hot_on,
+                         int* per_cu);
 };
 
 }  // namespace bc

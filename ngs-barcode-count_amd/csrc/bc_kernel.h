@@ -569,25 +569,46 @@ struct DeviceOps {
   uint32_t bytes, region, lane;
   uint32_t chunks;        // 1-KiB fetch instructions per full tile
   uint32_t pending_add;   // 1 while the previous tile's counter atomic may still be in flight
-  bool qual_async;        // this tile's quality lines were requested ahead of time
+  bool qual_async;        // this tile's quality lines were requested ahead of time (own region), or are requested
+                          // into the shared region once the sequence bytes are consumed
+  bool share;             // one region per wave, time-shared within a tile: seq(t), then qual(t), then seq(t+1)
 
   __device__ __forceinline__ bool any(bool c) const { return __any(c) != 0; }
   uint32_t abl_;  // experiment switches (0 outside BC_EXPERIMENT builds)
   bool defer_;            // captures that need the seed indexes are handed back (kDeferred), not searched at once
   __device__ __forceinline__ void issued() const { asm volatile("" ::: "memory"); }
-  // the sequence bytes are dead once the planes are built: the next tile's sequence lines can land
+  // the sequence bytes are dead once the planes are built: the next tile's sequence lines can land -- or, in a shared
+  // region, this tile's quality lines (the locate stage runs while they arrive)
   __device__ __forceinline__ void sequence_consumed() const {
     wave_lds_fence();
-    if (next_seq) dma_tile(tile, next_seq, 64u * (bytes_per_read()), lane);
+    if (share) {
+      if (qual_async) dma_tile(tile, qsrc, 64u * (bytes_per_read()), lane);
+    } else if (next_seq) {
+      dma_tile(tile, next_seq, 64u * (bytes_per_read()), lane);
+    }
+  }
+  // shared region: the quality bytes are dead once the runs are summed (the wrapping form included), and the next tile's
+  // sequence lines can land while the verdicts are drawn and the tile is counted.  Called when the table gathers that
+  // were in flight during the quality stage have been consumed: the compiler waits for ALL outstanding vector-memory
+  // operations at the use of an ordinary load while a tile fetch is in flight, so a fetch requested before that use
+  // would have to land there and then.
+  __device__ __forceinline__ void quality_consumed() const {
+    if (share && next_seq) {
+      __builtin_amdgcn_sched_barrier(0);  // (the uses of the gathers stay above)
+      wave_lds_fence();
+      dma_tile(tile, next_seq, 64u * (bytes_per_read()), lane);
+    }
   }
   __device__ __forceinline__ uint32_t bytes_per_read() const { return stride_; }
   uint32_t stride_;
   // younger: loads the lane code itself has in flight (issued after everything below)
   __device__ __forceinline__ const uint32_t* stage_quality(uint32_t younger) const {
     if (qual_async) {
-      // requested before the previous tile's counter atomic and the next tile's sequence lines: those
-      // (and the caller's own loads) may stay in flight
-      wait_vm_keep((next_seq ? chunks : 0u) + pending_add + younger);
+      // own region: requested before the previous tile's counter atomic and the next tile's sequence lines: those
+      // (and the caller's own loads) may stay in flight.  Shared region: requested in this tile, after the previous
+      // tile's log store or counter atomic and before the caller's loads: oldest first [log store / atomic] [quality
+      // lines] [the caller's loads] -- only the last may stay
+      wait_vm_keep(share ? younger : (next_seq ? chunks : 0u) + pending_add + younger);
       wave_lds_fence();
       return reinterpret_cast<const uint32_t*>(qtile);
     }
@@ -832,8 +853,9 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   if (tid < kNCounters) s_cnt[tid] = 0;
 
   const bool with_qual = pl.quality_on && !(pl.abl() & 0x8u);
-  // flags bit 0: software-pipelined tile fetch (two LDS regions per wave with the quality filter on);
-  // without it a wave has one region, filled on demand
+  // flags bit 0: software-pipelined tile fetch (with the quality filter on: two LDS regions per wave, or one that
+  // sequence and quality lines share in turn -- JIT_QSHARE, the specialised kernel only); without it a wave has one
+  // region, filled on demand
   // flags bit 1: the plan's exact-match tables are copied into LDS and used
   const bool pipe = (flags & 1u) != 0u;
 #ifdef JIT_LHASH
@@ -862,7 +884,12 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
       hot_cnt[i] = 0u;
     }
   }
-  const uint32_t two = (with_qual && pipe) ? 2u : 1u;
+#ifdef JIT_QSHARE
+  const bool share = JIT_QSHARE != 0 && with_qual;  // a constant: match_shape gives this shape to pipelined launches only
+#else
+  const bool share = false;  // the generic kernel keeps two regions: its wait counts are not immediates
+#endif
+  const uint32_t two = (with_qual && pipe && !share) ? 2u : 1u;
   // the waves' search queues sit between the cache and the tiles (the host reserves them whenever the plan has them:
   // lds_tiles_for)
   ops.defer_ = queues && !(pl.abl() & 0x200000u);
@@ -872,6 +899,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   ops.tile = reinterpret_cast<uint8_t*>(smem) + lhash_vec * 16u + (hot ? kHotBytes : 0u) + (queues ? (kTPB / 64) * kQueueBytes : 0u) +
              wave * region * two;
   ops.qtile = ops.tile + (two == 2u ? region : 0u);
+  ops.share = share;
   ops.region = region;
   ops.lane = lane;
   ops.stride_ = stride;
@@ -885,6 +913,10 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   // Software pipeline: while tile t is being matched, the sequence lines of the wave's next tile
   // are already on their way into the sequence region (free once t's bit planes exist), and t's
   // quality lines were requested at the end of the previous iteration.
+  // Shared region: the one region holds seq(t) until the planes exist, then qual(t) -- requested at that point, landing
+  // during the locate stage -- until the quality stage has summed its runs and the table gathers that were in flight
+  // beside it are consumed, then seq(t+1), landing while the verdicts are drawn and the tile is counted.  Nothing of
+  // tile t+1 is requested before tile t's quality stage is over.
   const uint64_t n_tiles = (n_reads + 63u) >> 6;
   const uint64_t n_full = n_reads >> 6;  // tiles with all 64 reads
   const uint64_t n_waves = (uint64_t)gridDim.x * (kTPB / 64);
@@ -892,9 +924,11 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
 #pragma unroll
   for (int k = 0; k < kNCounters; ++k) acc_cnt[k] = 0;
   // slack bytes behind the reads that the lane code may touch: plain values, written once
+  // (a shared region keeps 'A' for both: a base to the pack, a plain score to the quality stage, which never
+  // evaluates a run that reaches past its read)
   for (uint32_t i = full_bytes + lane; i < region; i += 64) {
     ops.tile[i] = 'A';
-    if (with_qual) ops.qtile[i] = 'I';
+    if (with_qual && !share) ops.qtile[i] = 'I';
   }
   // Two-level counting (`bits` given: large dense tables): the count of a tuple is bit + table entry.  A matched read
   // first tries to set its tuple's bit in a one-bit-per-tuple map -- 32 times denser than the table, so a good part of
@@ -915,7 +949,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   if (t < n_full && pipe) {
     dma_tile(ops.tile, seq + (t << 6) * stride, full_bytes, lane);
     seq_ready = true;
-    if (with_qual) {
+    if (with_qual && !share) {
       dma_tile(ops.qtile, qual + (t << 6) * stride, full_bytes, lane);
       qual_ready = true;
     }
@@ -958,10 +992,15 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     ops.qsrc = qual + goff;
     ops.bytes = n_w * stride;
     ops.next_seq = next_full ? seq + (tn << 6) * stride : nullptr;
-    ops.qual_async = qual_ready;
+    // (shared region: a full tile whose sequence lines came ahead of time gets its quality lines the same way, in-tile)
+    ops.qual_async = share ? seq_ready : qual_ready;
     if (seq_ready) {
       // outstanding, oldest first: [this tile's sequence lines] [its quality lines] [the previous tile's
-      // counter atomic] -- only the first must have landed
+      // counter atomic] -- only the first must have landed.  Shared region: [this tile's sequence lines] [whatever
+      // the previous tile issued after its quality stage and has consumed since] [its log store or counter atomic]
+      // (qual_ready stays false).  The count must not exceed what was really issued after seq(t), or the last chunks
+      // of seq(t) could be read before they land: pending_add counts one log store -- a tile that requested a next
+      // one is full, so the store under `if (active)` has lanes and is issued -- or atomics issued under a wave vote.
       wait_vm_keep((qual_ready ? ops.chunks : 0u) + ops.pending_add);
       wave_lds_fence();
     } else {
@@ -1012,7 +1051,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     // quality stage to arrive)
     seq_ready = next_full;
     qual_ready = false;
-    if (next_full && with_qual) {
+    if (next_full && with_qual && !share) {
       wave_lds_fence();
       dma_tile(ops.qtile, qual + (tn << 6) * stride, full_bytes, lane);
       qual_ready = true;

@@ -1039,6 +1039,15 @@ struct ReadResult {
 //   const uint32_t* stage_quality(uint32_t n)    -- called once, by every lane, when the quality filter is
 //                                                   on: returns where the quality lines are; n = loads of its
 //                                                   own the lane code still has in flight
+//   void quality_consumed()                      -- optional: called once, by every lane, after the last read of the
+//                                                   quality bytes and the use of the loads issued before them
+template <class Ops>
+BC_HD auto ops_quality_consumed(Ops& ops, int) -> decltype(ops.quality_consumed()) {
+  ops.quality_consumed();
+}
+template <class Ops>
+BC_HD void ops_quality_consumed(Ops&, long) {}  // an Ops without the hook
+
 // NW = 32-base words per read; NWW = words of candidate offsets / repair windows (len - L + 1 <= 32*NWW)
 // kAligned: base is a multiple of 4 for every lane (the stride is)
 template <class Ops, int NW, int NWW, bool kAligned = false>
@@ -1151,6 +1160,7 @@ BC_HD ReadResult process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32
   if (anyx) shr_lane<NW>(P.px, start);
   uint64_t didx = 0;
   bool raw_foreign = false;
+  bool quality_released = false;  // ops.quality_consumed() has been called
   const bool located = active && outcome == kMatched;  // anchored; the quality verdict is still to come
   const uint32_t ng = (pl.abl() & 0x20u) ? 0u : pl.n_groups;
   // four groups at a time: first every capture is cut out and looked up (LDS, then the table gathers
@@ -1352,6 +1362,13 @@ BC_HD ReadResult process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32
 #pragma unroll
     for (int u = 0; u < 4; ++u)
       if ((gather_m >> u) & 1u) r[u] = (tv[u] & 0xFFFFu) == (uint32_t)kFail16 ? kFail : (tv[u] & 0xFFFFu);
+    // The quality stage is over and none of this chunk's loads is in flight any more.  (Conservative: any ordinary
+    // load used later in the tile -- a further chunk's gathers in plans with more than four groups, the searches of
+    // ops.nearest, the atomic path's first-occurrence probe -- makes the fetch requested here land at that use.)
+    if (!quality_released) {
+      quality_released = true;
+      ops_quality_consumed(ops, 0);
+    }
     ops.mark(7);
     const bool pre_ok = active && outcome == kMatched;  // anchored and of good quality
 #pragma unroll
@@ -1386,6 +1403,7 @@ BC_HD ReadResult process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32
     }
   }
   if (!quality_done) quality_filter(0u);  // a scheme without barcode groups
+  if (!quality_released) ops_quality_consumed(ops, 0);
   // a later group may still have failed the read: then that failure is the outcome, as in the reference
   if (raw_foreign && outcome == kMatched) unsupported = true;
   // ---- random barcode: kept as captured, never corrected (parse.rs:510-516) ------------------
