@@ -270,9 +270,10 @@ int bc_engine_render_enriched_merged(bc_engine *e, int kind, const uint32_t *sam
  * Chunking, BC_RENDER_CHUNK_BYTES, the callback contract (`fn` != 0 -> BC_ERR_STATE, the engine still usable) and
  * BC_ERR_NOMEM are those of bc_engine_render_counts.
  * BC_ERR_UNSUPPORTED: a dense plan (use bc_engine_render_counts / _merged); a plan with wide keys
- * (bc_engine_key_words() > 1) or whose SAMPLE barcode is kept raw (its sample keys are captures, not indices,
- * info.rs:742-757) -- write those from bc_engine_finish + bc_engine_row_text on the host.  BC_ERR_INVALID: a sample index
- * out of range, a null callback, a null list with n_samples != 0. */
+ * (bc_engine_key_words() > 1: bc_engine_render_wide_counts / _merged below render those; the message still names the
+ * host path) or whose SAMPLE barcode is kept raw (its sample keys are captures, not indices, info.rs:742-757) -- write
+ * those from bc_engine_finish + bc_engine_row_text on the host.  BC_ERR_INVALID: a sample index out of range, a null
+ * callback, a null list with n_samples != 0. */
 int bc_engine_render_raw_counts(bc_engine *e, uint32_t sample_idx, bc_text_fn fn, void *user, uint64_t *n_rows);
 int bc_engine_render_raw_merged(bc_engine *e, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn, void *user,
                                 uint64_t *n_rows);
@@ -280,6 +281,33 @@ int bc_engine_render_raw_merged(bc_engine *e, const uint32_t *sample_idx, uint32
 int bc_engine_raw_render_sorts(const bc_engine *e, uint64_t *n);
 /* Device time of the last of them (export of the map, re-key, sort), in milliseconds, from HIP events; 0 before any. */
 int bc_engine_raw_render_sort_ms(const bc_engine *e, double *ms);
+
+/* The counts files of a wide-key plan (bc_engine_key_words() > 1: some counted barcode without a conversion file is longer
+ * than 27 bases, or the captures overflow one 64-bit key together -- README.md "Barcode-seq") as CSV text, written on the
+ * device.  Lines, layout, order and counts are those of bc_engine_render_raw_counts / _merged above, word for word: the
+ * digit of a raw capture is still  sum_k c_k * 5^k  (it no longer fits a word, the order is the same: captures compare
+ * from their LAST base backwards, A < C < T < G < N), so a scheme's files keep their order when a capture grows from 27
+ * to 28 bases.  For a random-barcode plan the count of a tuple is the number of its distinct random barcodes.
+ * The order is made on the device: the map is exported as bc_engine_finish exports it, every key is given an order key
+ * of K <= bc_engine_key_words() - 1 u64, the order keys are sorted word by word (a stable radix sort per word), and keys
+ * and counts are gathered into that order.  W = bc_engine_key_words(): at most (W + K) * 8 + 28.5 bytes per row while it
+ * runs, W * 8 + 4 bytes per row kept on the device afterwards, until something changes what bc_engine_finish would hand
+ * out: the renders of one state of the counts share one sort.
+ * Calls before or after bc_engine_finish, and more than once; on the root after bc_engine_finish_all they render the
+ * job's merged map.  Chunking, BC_RENDER_CHUNK_BYTES, the callback contract (`fn` != 0 -> BC_ERR_STATE, the engine still
+ * usable) and BC_ERR_NOMEM are those of bc_engine_render_counts.
+ * BC_ERR_UNSUPPORTED: a dense plan (use bc_engine_render_counts / _merged); a raw-key plan with one-word keys (use
+ * bc_engine_render_raw_counts / _merged); a plan whose SAMPLE barcode is kept raw (write it from bc_engine_finish +
+ * bc_engine_row_text on the host); 2^32 - 2048 rows or more.  BC_ERR_INVALID: a sample index out of range, a null
+ * callback, a null list with n_samples != 0. */
+int bc_engine_render_wide_counts(bc_engine *e, uint32_t sample_idx, bc_text_fn fn, void *user, uint64_t *n_rows);
+int bc_engine_render_wide_merged(bc_engine *e, const uint32_t *sample_idx, uint32_t n_samples, bc_text_fn fn, void *user,
+                                 uint64_t *n_rows);
+/* How many sorts the engine has made for those renders since it was created.  Read-only: does not wait for the device. */
+int bc_engine_wide_render_sorts(const bc_engine *e, uint64_t *n);
+/* Device time of the last of them (export of the map, order keys, sort, gather), in milliseconds, from HIP events; 0
+ * before any. */
+int bc_engine_wide_render_sort_ms(const bc_engine *e, double *ms);
 
 /* Row i as the reference's Results holds it (info.rs:661-665): the sample key (a sample barcode
  * sequence, or "barcode" without a sample group) and the counted barcodes "b1,b2,.." as sequences.

@@ -367,6 +367,31 @@ class Engine:
         _check(self._lib, self._lib.bc_engine_raw_render_sort_ms(self._e, C.byref(v)))
         return v.value
 
+    def render_wide_counts(self, sample=0, on_text=None):
+        """bc_engine_render_wide_counts: render_raw_counts() for a plan with wide keys (key words > 1: captures above 27
+        bases, or several that overflow one 64-bit key): the same lines in the same order, sorted and written on the
+        device.  Returns as render_counts does."""
+        return self._render(lambda fn, n: self._lib.bc_engine_render_wide_counts(self._e, int(sample), fn, None, n), on_text)
+
+    def render_wide_merged(self, samples, on_text=None):
+        """bc_engine_render_wide_merged: render_raw_merged() for a plan with wide keys."""
+        cols = np.ascontiguousarray(list(samples), dtype=np.uint32)
+        return self._render(lambda fn, n: self._lib.bc_engine_render_wide_merged(
+            self._e, cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
+
+    def wide_render_sorts(self):
+        """sorts made for render_wide_counts() / render_wide_merged() since the engine was created: the renders of one
+        state of the counts share one"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_wide_render_sorts(self._e, C.byref(n)))
+        return n.value
+
+    def wide_render_sort_ms(self):
+        """device milliseconds of the last of those sorts (map export, order keys, sort, gather)"""
+        v = C.c_double()
+        _check(self._lib, self._lib.bc_engine_wide_render_sort_ms(self._e, C.byref(v)))
+        return v.value
+
     def render_enriched(self, kind, sample=0, on_text=None):
         """bc_engine_render_enriched: the lines of sample index `sample`'s Single (kind = ENRICH_SINGLE) or Double
         (ENRICH_DOUBLE) file (no header), written on the device in ascending key order: G comma-joined fields of which

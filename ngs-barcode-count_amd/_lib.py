@@ -107,6 +107,10 @@ ENGINE_API = {
     "bc_engine_render_raw_merged": (_int, [_vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "bc_engine_raw_render_sorts": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_engine_raw_render_sort_ms": (_int, [_vp, C.POINTER(C.c_double)]),
+    "bc_engine_render_wide_counts": (_int, [_vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_render_wide_merged": (_int, [_vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_wide_render_sorts": (_int, [_vp, C.POINTER(C.c_uint64)]),
+    "bc_engine_wide_render_sort_ms": (_int, [_vp, C.POINTER(C.c_double)]),
     "bc_engine_timing": (_int, [_vp, _int]),
     "bc_engine_kernel_ms": (_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "bc_engine_kernel_ms_each": (_int, [_vp, C.POINTER(C.c_double), _u64, C.POINTER(C.c_uint64)]),

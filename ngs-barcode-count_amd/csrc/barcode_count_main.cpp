@@ -286,6 +286,7 @@ struct Run {
   // a raw-key plan's full-counts files sorted and written on the device (bc_engine_render_raw_counts / _merged;
   // BC_DEVICE_RAW_WRITERS=1): no rows on the host either
   bool raw_writers = false;
+  bool wide_keys = false;  // ... through bc_engine_render_wide_counts / _merged: the plan's keys are several words wide
   std::unordered_map<std::string, uint32_t> sample_index;  // sample key -> the engine's sample index
 };
 
@@ -557,6 +558,9 @@ uint64_t render_file(Run& r, const std::string& name, const std::string& head, c
   if (enriched)
     rc = merged ? bc_engine_render_enriched_merged(r.engine, enriched, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
                 : bc_engine_render_enriched(r.engine, enriched, cols[0], text_to_file, f, &n);
+  else if (r.raw_writers && r.wide_keys)
+    rc = merged ? bc_engine_render_wide_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
+                : bc_engine_render_wide_counts(r.engine, cols[0], text_to_file, f, &n);
   else if (r.raw_writers)
     rc = merged ? bc_engine_render_raw_merged(r.engine, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
                 : bc_engine_render_raw_counts(r.engine, cols[0], text_to_file, f, &n);
@@ -946,17 +950,18 @@ int main(int argc, char** argv) {
     }
   }
   // Raw-key plans (some counted barcode has no conversion file): with BC_DEVICE_RAW_WRITERS=1 the full-counts files are
-  // sorted and rendered on the device from the key map (bc_engine_render_raw_counts / _merged), which may change the
-  // order of the lines in those files and nothing else.  Kept on the rows: wide keys, a sample barcode kept raw (its
-  // samples are captures), enrichment (it needs the rows' strings), a counted file that names only some of the
+  // sorted and rendered on the device from the key map (bc_engine_render_raw_counts / _merged, or, for keys several
+  // words wide, bc_engine_render_wide_counts / _merged), which may change the order of the lines in those files and
+  // nothing else.  Kept on the rows: a sample barcode kept raw (its samples are captures), enrichment (it needs the rows' strings), a counted file that names only some of the
   // barcodes, and a sample file next to a scheme without a sample group (as above).
   const bool raw_plan = bc_plan_mode(r.plan) == 2;
   if (raw_plan) {
     const char* rw = getenv("BC_DEVICE_RAW_WRITERS");
     bool counted_whole = true;  // the counted file is absent, or names every counted barcode
     for (const auto& set : r.counted) counted_whole = counted_whole && !set.empty();
-    r.raw_writers = rw && strcmp(rw, "1") == 0 && bc_engine_key_words(r.engine) == 1 && (!sample_group || !r.samples.empty()) &&
-                    (sample_group || r.samples.empty()) && !r.args.enrich && counted_whole;
+    r.wide_keys = bc_engine_key_words(r.engine) > 1;
+    r.raw_writers = rw && strcmp(rw, "1") == 0 && (!sample_group || !r.samples.empty()) && (sample_group || r.samples.empty()) &&
+                    !r.args.enrich && counted_whole;
     if (r.raw_writers) {
       if (sample_group)
         for (uint32_t i = 0; i < r.samples.size(); ++i) r.sample_index[r.samples[i].first] = i;
@@ -973,7 +978,8 @@ int main(int argc, char** argv) {
             r.device_enrich ? "device text (bc_engine_render_enriched)" : "per-row strings");
   if (raw_plan && getenv("BC_WRITERS_VERBOSE"))  // (... of a raw-key plan)
     fprintf(stderr, "[barcode-count] raw writers: %s\n",
-            r.raw_writers ? "device text (bc_engine_render_raw_counts)" : "per-row strings");
+            !r.raw_writers ? "per-row strings"
+                           : (r.wide_keys ? "device text (bc_engine_render_wide_counts)" : "device text (bc_engine_render_raw_counts)"));
   if (!multi && !r.device_writers && !r.raw_writers && bc_engine_finish(r.engine, &n_rows)) die("%s", bc_last_error());
   r.counted_map.resize(r.counted.size());
   for (size_t b = 0; b < r.counted.size(); ++b)

@@ -562,6 +562,8 @@ static void engine_free(bc_engine* e) {
   if (e->d_sums) (void)hipFree(e->d_sums);
   if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
   if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
+  if (e->d_wide_keys) (void)hipFree(e->d_wide_keys);
+  if (e->d_wide_cnts) (void)hipFree(e->d_wide_cnts);
   if (e->d_counters) (void)hipFree(e->d_counters);
   if (e->d_plan) (void)hipFree(e->d_plan);
   if (e->reset_stream) (void)hipStreamSynchronize(e->reset_stream);
@@ -1489,11 +1491,59 @@ int bc::export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** 
   return BC_OK;
 }
 
+// wide keys (bc_long.h): the two steps of export_pairs on slots of key_words words
+int bc::export_wide(bc_engine* e, const char* who, ScratchGuard& g, unsigned long long** d_key, uint32_t** d_cnt,
+                    uint64_t* n_out) {
+  const DevPlan& P = e->h.plan;
+  unsigned long long* keys = e->d_slots;
+  uint32_t* vals = e->d_vals;
+  const uint64_t n_slots = e->n_slots;
+  const uint32_t W = e->key_words;
+  const uint32_t* ready = e->d_ready;
+  ScratchGuard agg;  // the table of tuples: gone when the rows are out
+  if (P.has_random) {
+    // count of a tuple = number of its distinct random barcodes (output.rs:265-270): every key, its random
+    // barcode's planes cleared, into a map of tuples
+    unsigned long long* agg_keys = nullptr;
+    uint32_t *agg_vals = nullptr, *agg_ready = nullptr;
+    HIP_TRY(agg.dmalloc(&agg_keys, n_slots * W * 8));
+    HIP_TRY(agg.dmalloc(&agg_vals, n_slots * 4));
+    HIP_TRY(agg.dmalloc(&agg_ready, n_slots * 4));
+    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots * W)), dim3(256), 0, e->stream, agg_keys, n_slots * W);
+    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
+    HIP_TRY(hipMemsetAsync(agg_ready, 0, n_slots * 4, e->stream));
+    hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_ready,
+                       (const uint32_t*)nullptr, n_slots, W, agg_keys, agg_ready, agg_vals, n_slots - 1, 1, e->lh.plan.rnd_bit,
+                       3u * e->lh.plan.rnd_len, (unsigned long long*)nullptr);
+    HIP_TRY(hipGetLastError());
+    keys = agg_keys;
+    vals = agg_vals;
+    ready = agg_ready;
+  }
+  unsigned long long* d_n = nullptr;
+  HIP_TRY(agg.dmalloc(&d_n, 8));
+  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
+  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);
+  HIP_TRY(g.dmalloc(d_key, cap * W * 8));
+  HIP_TRY(g.dmalloc(d_cnt, cap * 4));
+  hipLaunchKernelGGL(wide_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, ready, vals, n_slots, W, d_n, *d_key,
+                     *d_cnt, cap);
+  HIP_TRY(hipGetLastError());
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (n > cap) {  // (cannot happen: key_bound counts every insert)
+    set_error(std::string(who) + ": the key map holds more keys than its bound");
+    return BC_ERR_STATE;
+  }
+  *n_out = n;
+  return BC_OK;
+}
+
 extern "C" {
 
 // rows of a sparse plan: (tuple key, count) pairs straight out of the hash map
 static int finish_sparse(bc_engine* e, uint64_t* n_rows) {
-  const DevPlan& P = e->h.plan;
   e->row_idx.clear();
   e->row_cnt.clear();
   if (n_rows) *n_rows = 0;
@@ -1501,45 +1551,12 @@ static int finish_sparse(bc_engine* e, uint64_t* n_rows) {
   if (!e->d_slots) return BC_OK;
   ScratchGuard g;
   if (e->key_words > 1) {
-    // wide keys (bc_long.h): the two steps of export_pairs on slots of key_words words
-    unsigned long long* keys = e->d_slots;
-    uint32_t* vals = e->d_vals;
-    const uint64_t n_slots = e->n_slots;
     const uint32_t W = e->key_words;
-    const uint32_t* ready = e->d_ready;
-    if (P.has_random) {
-      // count of a tuple = number of its distinct random barcodes (output.rs:265-270): every key, its random
-      // barcode's planes cleared, into a map of tuples
-      unsigned long long* agg_keys = nullptr;
-      uint32_t *agg_vals = nullptr, *agg_ready = nullptr;
-      HIP_TRY(g.dmalloc(&agg_keys, n_slots * W * 8));
-      HIP_TRY(g.dmalloc(&agg_vals, n_slots * 4));
-      HIP_TRY(g.dmalloc(&agg_ready, n_slots * 4));
-      hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots * W)), dim3(256), 0, e->stream, agg_keys, n_slots * W);
-      HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
-      HIP_TRY(hipMemsetAsync(agg_ready, 0, n_slots * 4, e->stream));
-      hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_ready,
-                         (const uint32_t*)nullptr, n_slots, W, agg_keys, agg_ready, agg_vals, n_slots - 1, 1, e->lh.plan.rnd_bit,
-                         3u * e->lh.plan.rnd_len, (unsigned long long*)nullptr);
-      HIP_TRY(hipGetLastError());
-      keys = agg_keys;
-      vals = agg_vals;
-      ready = agg_ready;
-    }
-    unsigned long long* d_n = nullptr;
     unsigned long long* d_key = nullptr;
     uint32_t* d_cnt = nullptr;
-    HIP_TRY(g.dmalloc(&d_n, 8));
-    HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-    const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);
-    HIP_TRY(g.dmalloc(&d_key, cap * W * 8));
-    HIP_TRY(g.dmalloc(&d_cnt, cap * 4));
-    hipLaunchKernelGGL(wide_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, ready, vals, n_slots, W, d_n, d_key,
-                       d_cnt, cap);
-    HIP_TRY(hipGetLastError());
-    unsigned long long n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    uint64_t n = 0;
+    const int rc = export_wide(e, "bc_engine_finish", g, &d_key, &d_cnt, &n);
+    if (rc != BC_OK) return rc;
     try {
       e->row_wide.resize(n * W);
       e->row_cnt.resize(n);

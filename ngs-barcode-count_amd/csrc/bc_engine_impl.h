@@ -179,6 +179,14 @@ struct bc_engine {
   uint64_t raw_n = 0;
   uint64_t raw_sorts = 0;                // sorts made since the engine was created (bc_engine_raw_render_sorts)
   float raw_sort_ms = 0.f;               // export + re-key + sort of the last one, from HIP events
+  // The wide-key renderer (bc_wide_render.h): the exported keys (key_words u64 each) and counts gathered into the order
+  // of the files, kept on the device under the counts epoch exactly as d_raw_keys is.
+  uint64_t wide_epoch = 0;
+  uint64_t* d_wide_keys = nullptr;
+  uint32_t* d_wide_cnts = nullptr;
+  uint64_t wide_n = 0;
+  uint64_t wide_sorts = 0;               // sorts made since the engine was created (bc_engine_wide_render_sorts)
+  float wide_sort_ms = 0.f;              // export + order keys + sort + gather of the last one, from HIP events
 };
 
 namespace bc {
@@ -197,6 +205,10 @@ bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t
 // The (tuple key, count) pairs of a narrow-key map as they stand, into buffers that `g` owns: a random-barcode plan's key
 // set first aggregated into per-tuple distinct counts.  e->d_slots is not NULL; the stream has drained on return.
 int export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** d_key, uint32_t** d_cnt, uint64_t* n);
+// The same for a wide-key map (bc_long.h): n keys of e->key_words words each, and their counts, a random-barcode plan's
+// key set first re-inserted with its random planes cleared.  What bc_engine_finish hands out and the wide-key renderer
+// sorts.  e->d_slots is not NULL; the stream has drained on return.
+int export_wide(bc_engine* e, const char* who, ScratchGuard& g, unsigned long long** d_key, uint32_t** d_cnt, uint64_t* n);
 
 }  // namespace bc
 

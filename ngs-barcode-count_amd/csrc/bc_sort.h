@@ -1,6 +1,7 @@
 // bc_sort.h -- stable LSD radix sort of (u64 key, u32 value) pairs on the device: the order of a raw-key plan's counts
 // files (bc_raw_render.h).  Plain HIP kernels, compiled with whoever includes this header (the engine, and the test
-// harness tests/sort/sort_harness.hip); one entry point, bc::sort_pairs_launch.
+// harness tests/sort/sort_harness.hip); one entry point, bc::sort_pairs_launch -- and, built on it at the end of this
+// file, bc::sort_words_launch: the order of keys several u64 wide (bc_wide_render.h; tests/sort/sort_words_harness.hip).
 //
 // Eight bits per pass, least significant byte first; only the passes below key_bits run.
 //   before the passes  sort_ghist_kernel   the global digit histogram of EVERY pass in one sweep of the keys (the
@@ -234,6 +235,56 @@ inline hipError_t sort_pairs_launch(hipStream_t stream, uint64_t* keys_in, uint3
     if ((rc = hipMemcpyAsync(vals_in, vals_tmp, n * 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return rc;
   }
   if (live_passes) *live_passes = live;
+  return hipSuccess;
+}
+
+// ---- keys of several words (bc_wide_render.h) ----
+
+__global__ __launch_bounds__(256) void sort_iota_kernel(uint32_t* __restrict__ perm, uint32_t n) {
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) perm[i] = (uint32_t)i;
+}
+
+// col[j] = word[perm[j]]: one word of every key, in the order the passes before have made
+__global__ __launch_bounds__(256) void sort_column_kernel(const unsigned long long* __restrict__ word,
+                                                          const uint32_t* __restrict__ perm, uint32_t n,
+                                                          unsigned long long* __restrict__ col) {
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += step) {
+    const uint32_t i = perm[j];
+    col[j] = i < n ? word[i] : 0ull;  // (always: perm is a permutation of 0 .. n-1)
+  }
+}
+
+// The order of n keys of K u64 words each, compared word by word as unsigned numbers with word K-1 the most significant:
+// perm[j] = the index of the key that comes j-th, keys equal in every word in ascending index (the sort is stable).
+// words: K columns of n entries, word w of key i at words[w * n + i]; they are only read.
+// LSD over the words, least significant first: per word, its column gathered in the order made so far and sorted with the
+// permutation as the value by sort_pairs_launch -- whose stability is what carries the lower words' order through, and
+// whose skipped passes make a word that all keys share cost one histogram sweep.
+// col, col_tmp: n u64 each; perm_tmp: n u32; scratch: sort_scratch_words(n) u32.  Enqueues on `stream` and waits for it
+// once per word.  n == 0 launches nothing; n at or above 2^32 - kSortTile: hipErrorInvalidValue.
+// Device memory beside the keys' K x 8 n bytes: 4 n (perm) + 16 n + 4 n + n / 2 + 8 KiB = 24.5 n bytes + 8 KiB.
+// live_passes (may be NULL): the passes that moved data, over all words.
+inline hipError_t sort_words_launch(hipStream_t stream, const uint64_t* words, uint32_t K, uint64_t n, uint32_t* perm,
+                                    uint64_t* col, uint64_t* col_tmp, uint32_t* perm_tmp, uint32_t* scratch,
+                                    uint32_t* live_passes = nullptr) {
+  if (live_passes) *live_passes = 0;
+  if (n == 0) return hipSuccess;
+  if (n >= 0xFFFFFFFFull - kSortTile || K == 0) return hipErrorInvalidValue;
+  const uint32_t n32 = (uint32_t)n;
+  const uint32_t grid = (uint32_t)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+  hipLaunchKernelGGL(sort_iota_kernel, dim3(grid), dim3(256), 0, stream, perm, n32);
+  hipError_t rc = hipGetLastError();
+  if (rc != hipSuccess || n < 2) return rc;
+  for (uint32_t w = 0; w < K; ++w) {
+    hipLaunchKernelGGL(sort_column_kernel, dim3(grid), dim3(256), 0, stream, (const unsigned long long*)words + (uint64_t)w * n,
+                       (const uint32_t*)perm, n32, (unsigned long long*)col);
+    if ((rc = hipGetLastError()) != hipSuccess) return rc;
+    uint32_t live = 0;
+    if ((rc = sort_pairs_launch(stream, col, perm, col_tmp, perm_tmp, n, 64, scratch, &live)) != hipSuccess) return rc;
+    if (live_passes) *live_passes += live;
+  }
   return hipSuccess;
 }
 

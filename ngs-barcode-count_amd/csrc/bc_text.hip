@@ -1,7 +1,8 @@
 // bc_text.hip -- the output files written as CSV text on the device: the counts files of a dense plan
 // (bc_engine_render_counts / _merged; lane code bc_render.h), the Single and Double enrichment files
 // (bc_engine_render_enriched / _merged; bc_enrich_render.h) and the sorted counts files of a raw-key plan
-// (bc_engine_render_raw_counts / _merged; bc_raw_render.h, bc_sort.h).  A renderer is a view struct with lane code and a
+// (bc_engine_render_raw_counts / _merged; bc_raw_render.h, bc_sort.h) and of a wide-key plan
+// (bc_engine_render_wide_counts / _merged; bc_wide_render.h, bc_sort.h).  A renderer is a view struct with lane code and a
 // front end that checks the request and fills the view; the kernels (bc_text_kernels.h) and the host loop around them
 // (stream_text) are templates over the view.
 #include <hip/hip_runtime.h>
@@ -18,10 +19,11 @@
 #include "bc_raw_render.h"
 #include "bc_sort.h"
 #include "bc_text_kernels.h"
+#include "bc_wide_render.h"
 
 using namespace bc;
 
-// ---- what the three renderers share ----
+// ---- what the renderers share ----
 
 // The IDs of the counted sets on the device, once per engine: per group N_g + 1 offsets, and the bytes back to back.
 static int ensure_render_pool(bc_engine* e, const char* who) {
@@ -486,6 +488,232 @@ int bc_engine_raw_render_sorts(const bc_engine* e, uint64_t* n) {
 
 int bc_engine_raw_render_sort_ms(const bc_engine* e, double* ms) {
   *ms = (double)e->raw_sort_ms;
+  return BC_OK;
+}
+
+}  // extern "C"
+
+// ---- counts of a wide-key plan as text (bc_wide_render.h, bc_sort.h) ----
+
+namespace bc {
+
+// okeys[w * n + i] = word w of the order key of key i (blockIdx.y = w): a lane makes one word of one key
+__global__ __launch_bounds__(256) void wide_order_kernel(WideOrder o, const unsigned long long* __restrict__ keys, uint64_t n,
+                                                         unsigned long long* __restrict__ okeys) {
+  const uint32_t w = blockIdx.y;
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+    okeys[(uint64_t)w * n + i] = wide_order_word(o, (const uint64_t*)keys + i * o.W + 1u, w);
+}
+
+// the keys (W words each) and counts into file order: entry j comes from perm[j]; a lane moves one word
+__global__ __launch_bounds__(256) void wide_gather_kernel(const unsigned long long* __restrict__ keys,
+                                                          const uint32_t* __restrict__ cnts, const uint32_t* __restrict__ perm,
+                                                          uint64_t n, uint32_t W, unsigned long long* __restrict__ keys_out,
+                                                          uint32_t* __restrict__ cnts_out) {
+  const uint64_t total = n * W, step = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+    const uint64_t j = (t >> 32) == 0 ? (uint64_t)((uint32_t)t / W) : t / W;
+    const uint32_t w = (uint32_t)(t - j * W);
+    const uint64_t i = perm[j];
+    if (i >= n) continue;  // (never: perm is a permutation of 0 .. n-1)
+    keys_out[t] = keys[i * W + w];
+    if (w == 0) cnts_out[j] = cnts[i];
+  }
+}
+
+}  // namespace bc
+
+static void wide_sorted_drop(bc_engine* e) {
+  if (e->d_wide_keys) (void)hipFree(e->d_wide_keys);
+  if (e->d_wide_cnts) (void)hipFree(e->d_wide_cnts);
+  e->d_wide_keys = nullptr;
+  e->d_wide_cnts = nullptr;
+  e->wide_n = 0;
+  e->wide_epoch = 0;
+}
+
+// The keys and counts of the current counts in the order of the files, in e->d_wide_keys / d_wide_cnts (wide_n of them,
+// n x (W x 8 + 4) bytes): served as they are while the counts epoch stands, else exported from the map (export_wide, as
+// bc_engine_finish does), given order keys, sorted by them (bc::sort_words_launch) and gathered.  Peak device memory per
+// exported row, beside the map: while the sort runs the exported row (W x 8 + 4), its order key (K x 8) and the sort's
+// 24.5 bytes -- (W + K) x 8 + 28.5; order keys and sort buffers are released before the gather, which holds the row
+// twice and the permutation -- 2 x (W x 8 + 4) + 4.  With K <= W - 1 <= 7 that is at most 148.5 bytes per row.  (A random-
+// barcode plan's export holds its table of tuples, slots x (W x 8 + 8) bytes, until the rows are out, before any of it.)
+static int ensure_wide_sorted(bc_engine* e, const bc::WideOrder& o) {
+  if (e->wide_epoch == e->counts_epoch) return BC_OK;
+  wide_sorted_drop(e);
+  if (!e->d_slots) {  // nothing was ever submitted or imported
+    e->wide_epoch = e->counts_epoch;
+    return BC_OK;
+  }
+  ScratchGuard g;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIP_TRY(hipEventCreate(&ev0));
+  g.events.push_back(ev0);
+  HIP_TRY(hipEventCreate(&ev1));
+  g.events.push_back(ev1);
+  HIP_TRY(hipEventRecord(ev0, e->stream));
+  unsigned long long* d_key = nullptr;
+  uint32_t* d_cnt = nullptr;
+  uint64_t n = 0;
+  const int rc = export_wide(e, "wide render", g, &d_key, &d_cnt, &n);
+  if (rc != BC_OK) return rc;
+  if (n >= 0xFFFFFFFFull - bc::kSortTile) {
+    set_error("wide render: " + std::to_string(n) + " rows pass what one sort takes (2^32); write them from bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  const uint32_t W = o.W;
+  unsigned long long* d_key2 = nullptr;
+  uint32_t* d_cnt2 = nullptr;
+  if (n) {
+    uint32_t* d_perm = nullptr;
+    HIP_TRY(g.dmalloc(&d_perm, n * 4));
+    {
+      ScratchGuard s;  // order keys and the sort's buffers: gone before the gather's destination is made
+      unsigned long long* d_okeys = nullptr;
+      uint64_t *d_col = nullptr, *d_col2 = nullptr;
+      uint32_t *d_perm2 = nullptr, *d_scratch = nullptr;
+      HIP_TRY(s.dmalloc(&d_okeys, n * o.K * 8));
+      HIP_TRY(s.dmalloc(&d_col, n * 8));
+      HIP_TRY(s.dmalloc(&d_col2, n * 8));
+      HIP_TRY(s.dmalloc(&d_perm2, n * 4));
+      HIP_TRY(s.dmalloc(&d_scratch, bc::sort_scratch_words(n) * 4));
+      hipLaunchKernelGGL(wide_order_kernel, dim3(std::min<uint32_t>(grid_for(n), 2048u), o.K), dim3(256), 0, e->stream, o, d_key, n,
+                         d_okeys);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(bc::sort_words_launch(e->stream, (const uint64_t*)d_okeys, o.K, n, d_perm, d_col, d_col2, d_perm2, d_scratch));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    HIP_TRY(g.dmalloc(&d_key2, n * W * 8));
+    HIP_TRY(g.dmalloc(&d_cnt2, n * 4));
+    hipLaunchKernelGGL(wide_gather_kernel, dim3(grid_for(n * W)), dim3(256), 0, e->stream, d_key, d_cnt, d_perm, n, W, d_key2, d_cnt2);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(ev1, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  (void)hipEventElapsedTime(&e->wide_sort_ms, ev0, ev1);
+  for (void* keep : {(void*)d_key2, (void*)d_cnt2})
+    if (keep) g.dev.erase(std::find(g.dev.begin(), g.dev.end(), keep));
+  e->d_wide_keys = (uint64_t*)d_key2;
+  e->d_wide_cnts = d_cnt2;
+  e->wide_n = n;
+  e->wide_epoch = e->counts_epoch;
+  ++e->wide_sorts;
+  return BC_OK;
+}
+
+static int render_wide(bc_engine* e, const char* who, bool merged, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
+                       void* user, uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (!P.sparse) {
+    set_error(std::string(who) + ": the plan has a dense table: its files come from bc_engine_render_counts / "
+              "bc_engine_render_merged");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
+    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: write the rows "
+              "from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->key_words <= 1) {
+    set_error(std::string(who) + ": the plan's keys are one word wide: its files come from bc_engine_render_raw_counts / "
+              "bc_engine_render_raw_merged");
+    return BC_ERR_UNSUPPORTED;
+  }
+  const LongPlan& Q = e->lh.plan;  // (a wide-key plan is the wave-per-read kernel's: its groups hold the key layout)
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  const uint32_t S = g0 ? Q.groups[0].n_refs : 1u;
+  int rc = check_request(who, cols, n_cols, fn, S);
+  if (rc) return rc;
+  bc::WideRenderView v;
+  bc::WideOrder o;
+  memset(&v, 0, sizeof v);
+  memset(&o, 0, sizeof o);
+  v.G = o.G = e->barcode_num;
+  v.W = o.W = e->key_words;
+  v.S = S;
+  v.merged = merged ? 1u : 0u;
+  v.sample = n_cols ? cols[0] : 0u;
+  v.n_cols = n_cols;
+  // (cannot happen: a plan's groups fit the view, its sample group comes first and starts the payload)
+  if (v.G > (uint32_t)bc::kRenderMaxG || g0 + v.G > Q.n_groups || v.W > (uint32_t)kMaxKeyWords ||
+      (g0 && (Q.groups[0].type != kGroupSample || Q.groups[0].key_bit != 0))) {
+    set_error(std::string(who) + ": the plan's groups do not fit the view");
+    return BC_ERR_STATE;
+  }
+  v.sample_bits = o.sample_bits = g0 ? 32u : 0u;
+  o.sample_obits = g0 ? bc::wide_bit_length(S - 1u) : 0u;
+  const uint32_t pay_bits = 64u * (v.W - 1u);
+  for (uint32_t g = 0; g < v.G; ++g) {
+    const LongGroup& G = Q.groups[g0 + g];
+    v.key_bit[g] = o.key_bit[g] = G.key_bit;
+    if (G.n_refs == 0) {
+      v.raw_len[g] = o.raw_len[g] = G.len;
+    } else {
+      v.n_ids[g] = G.n_refs;
+      o.obits[g] = bc::wide_bit_length(G.n_refs - 1u);
+    }
+    if (G.key_bit + (G.n_refs ? 32u : 3u * G.len) > pay_bits || (G.n_refs == 0 && G.len == 0)) {  // (cannot happen)
+      set_error(std::string(who) + ": a group's field lies outside the key");
+      return BC_ERR_STATE;
+    }
+  }
+  bc::wide_order_layout(o);
+  if (o.K + 1u > v.W) {  // (cannot happen: no field is wider in the order key than in the payload)
+    set_error(std::string(who) + ": the order key is wider than the key");
+    return BC_ERR_STATE;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if ((rc = bc_engine_sync(e)) != BC_OK) return rc;  // the submits, as bc_engine_finish waits for them
+  if ((rc = ensure_wide_sorted(e, o)) != BC_OK) return rc;
+  if (n_cols == 0 || e->wide_n == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < v.G; ++g) {
+    if (v.raw_len[g]) {
+      max_line += v.raw_len[g];
+    } else {
+      if (bc_plan_n_counted(e->src_plan, g) != v.n_ids[g]) {  // (cannot happen: the key's indices are the plan's sets)
+        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+        return BC_ERR_STATE;
+      }
+      v.off_start[g] = e->label_off_start[g];
+      max_line += e->label_max[g];
+    }
+  }
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
+  v.keys = e->d_wide_keys;
+  v.cnts = e->d_wide_cnts;
+  v.n = e->wide_n;
+  v.cols = d_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+extern "C" {
+
+int bc_engine_render_wide_counts(bc_engine* e, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_wide(e, "bc_engine_render_wide_counts", false, &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_wide_merged(bc_engine* e, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn, void* user,
+                                 uint64_t* n_rows) {
+  return render_wide(e, "bc_engine_render_wide_merged", true, sample_idx, n_samples, fn, user, n_rows);
+}
+
+int bc_engine_wide_render_sorts(const bc_engine* e, uint64_t* n) {
+  *n = e->wide_sorts;
+  return BC_OK;
+}
+
+int bc_engine_wide_render_sort_ms(const bc_engine* e, double* ms) {
+  *ms = (double)e->wide_sort_ms;
   return BC_OK;
 }
 
