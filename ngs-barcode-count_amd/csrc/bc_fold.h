@@ -5,6 +5,7 @@
 //   bc_fold_hist     entries per bucket (a bucket = 2^22 tuples = 512 KB of bit map; at most 1024 buckets)
 //   bc_fold_scan     bucket starts, and the fold's work items (bucket x chunk of entries)
 //   bc_fold_scatter  the log grouped by bucket: 16384-entry tiles sorted in LDS, then written out as runs
+//                    (the tile held in registers meanwhile, the next tile's loads in flight)
 //   bc_fold_apply    per item and quarter of its bucket: 128 KB of bit map into LDS, one LDS atomicOr per entry (a bit
 //                    that was set already makes the entry a table add), the quarter written back
 // A tuple with c entries ends as the atomic path would leave it: bit clear before -> bit set and table + c - 1; bit set
@@ -12,6 +13,10 @@
 // then meet on the same quarter: there the first entry of a tuple in an item also sets its bit in memory, with a
 // returning atomicOr, and a bit another item had set meanwhile was not a first occurrence after all (table + 1).
 // Exactly one of them sets each bit; only the sole item of a bucket writes its quarters back whole.
+// Neither kernel waits for one memory access at a time: loads go out as 16-byte groups, several together and ahead of
+// their use, and a thread's LDS atomics are issued back to back with one wait behind them.  log and grouped are
+// therefore 16-byte aligned (fold_launch refuses others), and no load reaches past the 16-byte group that holds the
+// last entry of the log or of an item.
 //
 // A fold onto a map that is known to be all zero but has not been written so (`fresh`: the engine's first fold after a
 // reset, bc_engine.hip) reads none of it: the sole item of a bucket starts its quarters from zeroed LDS and writes them
@@ -29,8 +34,14 @@ constexpr uint32_t kFoldMaxBuckets = 1024;  // indexes below 2^32
 constexpr uint32_t kFoldTile = 16384;       // bc_fold_scatter: entries per LDS tile (two workgroups per CU)
 constexpr uint32_t kFoldChunk = 1u << 18;   // entries per apply item at most
 constexpr uint32_t kFoldQuarterWords = 1u << (kFoldQuarterShift - 5);
-constexpr uint32_t kFoldScatterLds = kFoldTile * 4u + 3u * kFoldMaxBuckets * 4u;
+constexpr uint32_t kFoldSpare = 64;          // bc_fold_scatter: bins behind the buckets' for kLogNone entries, one per lane
+constexpr uint32_t kFoldScatterLds = kFoldTile * 4u + (3u * kFoldMaxBuckets + 2u * kFoldSpare) * 4u;
 constexpr uint32_t kFoldApplyLds = kFoldQuarterWords * 4u;
+
+// A workgroup barrier that orders LDS alone: loads, stores and atomics to global memory that are in flight stay in
+// flight across it (__syncthreads waits for them).  Scatter and apply place every wait for memory themselves: both
+// request entries well ahead of their use.
+__device__ __forceinline__ void fold_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // exclusive prefix sum over the 1024 threads of a workgroup; tmp: 16 words of LDS.  Returns the total in `total`.
 __device__ __forceinline__ uint32_t fold_block_scan(uint32_t v, uint32_t* tmp, uint32_t& total) {
@@ -100,54 +111,101 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_scan(uint32_t* __restrict__ 
   }
 }
 
+// A tile's entries are read once, as four 16-byte loads per thread that are all in flight together, and stay in
+// registers from the ranking to the placement; the loads of the workgroup's next tile are requested before the current
+// tile is written out.  Every tile but the last takes the loads without a bounds test; in the last, what lies past n
+// counts as kLogNone (no load reaches beyond the 16-byte group of the log's last entry: the log is 16-byte aligned).
+// A kLogNone entry takes its rank from a spare bin and is placed on that bin, so neither pass branches around its
+// LDS operation and the sixteen of a thread are issued back to back.
 __global__ __launch_bounds__(kFoldTPB) void bc_fold_scatter(const uint32_t* __restrict__ log, uint64_t n, uint32_t nb,
                                                            uint32_t* __restrict__ cursor, uint32_t* __restrict__ out) {
   extern __shared__ uint32_t fold_smem[];
   uint32_t* sorted = fold_smem;
   uint32_t* h = sorted + kFoldTile;
-  uint32_t* lstart = h + kFoldMaxBuckets;
-  uint32_t* base = lstart + kFoldMaxBuckets;
+  uint32_t* lstart = h + kFoldMaxBuckets + kFoldSpare;
+  uint32_t* base = lstart + kFoldMaxBuckets + kFoldSpare;
   __shared__ uint32_t tmp[kFoldTPB / 64u];
   const uint32_t tid = threadIdx.x;
-  constexpr uint32_t kPer = kFoldTile / kFoldTPB;
-  const uint64_t n_tiles = (n + kFoldTile - 1u) / kFoldTile;
-  for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const uint64_t t0 = t * kFoldTile;
-    for (uint32_t i = tid; i < kFoldMaxBuckets; i += kFoldTPB) h[i] = 0;
-    __syncthreads();
-    // the entries' ranks within their bucket, two per register (below 2^15); the entries themselves are read again
-    // below (from the L2) rather than held in registers
+  constexpr uint32_t kPer = kFoldTile / kFoldTPB, kPer4 = kPer / 4u;
+  const uint64_t n_tiles = (n + kFoldTile - 1u) / kFoldTile, n_full = n / kFoldTile;
+  const uint4* log4 = reinterpret_cast<const uint4*>(log);
+  const uint32_t spare = kFoldMaxBuckets + (tid & (kFoldSpare - 1u));  // one per lane: no two lanes of a wave meet there
+  uint32_t x[kPer];
+  auto request = [&](uint64_t t) {
+    const uint4* p = log4 + t * (kFoldTile / 4u) + tid;
+    if (t < n_full) {
+#pragma unroll
+      for (uint32_t k = 0; k < kPer4; ++k) {
+        const uint4 v = p[k * kFoldTPB];
+        x[4 * k + 0] = v.x, x[4 * k + 1] = v.y, x[4 * k + 2] = v.z, x[4 * k + 3] = v.w;
+      }
+    } else {
+      const uint32_t n_t = (uint32_t)(n - t * kFoldTile);
+#pragma unroll
+      for (uint32_t k = 0; k < kPer4; ++k) {
+        const uint32_t e = (k * kFoldTPB + tid) * 4u;
+        const uint4 v = e < n_t ? p[k * kFoldTPB] : make_uint4(kLogNone, kLogNone, kLogNone, kLogNone);
+        x[4 * k + 0] = e + 0u < n_t ? v.x : kLogNone;
+        x[4 * k + 1] = e + 1u < n_t ? v.y : kLogNone;
+        x[4 * k + 2] = e + 2u < n_t ? v.z : kLogNone;
+        x[4 * k + 3] = e + 3u < n_t ? v.w : kLogNone;
+      }
+    }
+  };
+  uint64_t t = blockIdx.x;
+  if (t < n_tiles) request(t);
+  // the run of a spare bin is the bin itself (h follows sorted): where the placement puts a kLogNone entry
+  if (tid < kFoldSpare) lstart[kFoldMaxBuckets + tid] = kFoldTile + kFoldMaxBuckets + tid;
+  for (; t < n_tiles; t += gridDim.x) {
+    // (the last tile's write-out reads none of h, so no barrier stands between it and these stores)
+    for (uint32_t i = tid; i < kFoldMaxBuckets + kFoldSpare; i += kFoldTPB) h[i] = 0;
+    fold_lds_barrier();
+    // the entries' ranks within their bucket, two per register (below 2^15)
     uint32_t r[kPer / 2];
-    const uint32_t* tl = log + t0 + tid;
-    const uint32_t n_t = n - t0 < kFoldTile ? (uint32_t)(n - t0) : kFoldTile;
 #pragma unroll
     for (uint32_t k = 0; k < kPer; ++k) {
-      const uint32_t v = k * kFoldTPB + tid < n_t ? tl[k * kFoldTPB] : kLogNone;
-      const uint32_t rk = v != kLogNone ? atomicAdd(&h[v >> kFoldBucketShift], 1u) : 0u;
+      const uint32_t rk = atomicAdd(&h[x[k] != kLogNone ? x[k] >> kFoldBucketShift : spare], 1u);  // (a load-free select)
       if (k & 1u) r[k / 2] |= rk << 16; else r[k / 2] = rk;
     }
-    __syncthreads();
+    fold_lds_barrier();
     // one bucket per thread (nb <= 1024): the tile's runs, and their places in the grouped log
     const uint32_t hc = tid < nb ? h[tid] : 0u;
     uint32_t valid;
     const uint32_t ls = fold_block_scan(hc, tmp, valid);
+    uint32_t reserved = 0;
     if (tid < nb) {
       lstart[tid] = ls;
-      if (hc) base[tid] = atomicAdd(&cursor[tid], hc);
+      if (hc) reserved = atomicAdd(&cursor[tid], hc);
     }
-    __syncthreads();
+    fold_lds_barrier();
+    // the placement needs lstart alone: the reservation is in flight beside it.  Eight runs are read before the eight
+    // entries go to their places (reads and writes of the one LDS array are not reordered by the compiler)
 #pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k) {
-      const uint32_t v = k * kFoldTPB + tid < n_t ? tl[k * kFoldTPB] : kLogNone;
-      if (v != kLogNone) sorted[lstart[v >> kFoldBucketShift] + ((r[k / 2] >> (16u * (k & 1u))) & 0xFFFFu)] = v;
+    for (uint32_t k0 = 0; k0 < kPer; k0 += 8u) {
+      uint32_t at[8];
+#pragma unroll
+      for (uint32_t k = k0; k < k0 + 8u; ++k) {
+        const uint32_t rk = (r[k / 2] >> (16u * (k & 1u))) & 0xFFFFu;
+        const bool some = x[k] != kLogNone;
+        at[k - k0] = lstart[some ? x[k] >> kFoldBucketShift : spare] + (some ? rk : 0u);
+      }
+#pragma unroll
+      for (uint32_t k = k0; k < k0 + 8u; ++k) sorted[at[k - k0]] = x[k];
     }
-    __syncthreads();
-    for (uint32_t i = tid; i < valid; i += kFoldTPB) {
-      const uint32_t x = sorted[i];
-      const uint32_t bk = x >> kFoldBucketShift;
-      out[base[bk] + (i - lstart[bk])] = x;
+    if (tid < nb && hc) base[tid] = reserved;
+    if (t + gridDim.x < n_tiles) request(t + gridDim.x);
+    fold_lds_barrier();
+    // sixteen entries per thread again, without a branch around their LDS reads: a thread whose place lies past the
+    // tile's last valid entry writes that entry once more (the same word to the same place)
+    if (valid) {
+#pragma unroll
+      for (uint32_t k = 0; k < kPer; ++k) {
+        const uint32_t i = k * kFoldTPB + tid < valid ? k * kFoldTPB + tid : valid - 1u;
+        const uint32_t v = sorted[i];
+        const uint32_t bk = v >> kFoldBucketShift;
+        out[base[bk] + (i - lstart[bk])] = v;
+      }
     }
-    __syncthreads();
   }
 }
 
@@ -179,98 +237,168 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_zero_unowned(uint32_t nb, co
 }
 
 // n_words: bit-map words in use (ceil(entries / 32)); dirty: the table's dirty-block map, or null; fresh: the map counts
-// as all zero whatever memory holds (the owner of a bucket does not load it; bc_fold_zero_unowned has run)
+// as all zero whatever memory holds (the owner of a bucket does not load it; bc_fold_zero_unowned has run).
+// A workgroup's entries arrive in batches of sixteen per thread, and a batch is requested before the one ahead of it is
+// processed: the next batch of the quarter, else the first batch of the next quarter (the same entries again, from the
+// L2), else the first batch of the workgroup's next item -- none of which depends on what LDS holds, so they stay in
+// flight across the barriers (fold_lds_barrier).  Every request is clipped to its item.
 __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __restrict__ grouped, uint32_t nb,
                                                          const uint32_t* __restrict__ start, const uint32_t* __restrict__ item_off,
                                                          uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ table,
                                                          uint8_t* __restrict__ dirty, uint32_t fresh) {
+  static_assert(kFoldMaxBuckets <= kFoldTPB, "one bucket per thread");
   extern __shared__ uint32_t fold_smem[];
   uint4* q4 = reinterpret_cast<uint4*>(fold_smem);
+  // the item in turn and the workgroup's next one: bucket, sole item of its bucket, first entry, end of its entries
+  __shared__ uint32_t s_item[2][4];
   const uint32_t tid = threadIdx.x;
   constexpr uint32_t kPer = kFoldQuarterWords / 4u / kFoldTPB;  // uint4 per thread
+  constexpr uint32_t kIn4 = 4;                                   // 16-byte loads per thread and batch
+  constexpr uint32_t kBatch = kIn4 * 4u * kFoldTPB;
+  const uint4 none4 = make_uint4(kLogNone, kLogNone, kLogNone, kLogNone);
   const uint32_t n_items = item_off[nb];
+  uint32_t it = blockIdx.x;
+  if (it >= n_items) return;
   auto add = [&](uint32_t idx) {
     table_add(&table[idx]);
     if (dirty) dirty[idx >> 6] = (uint8_t)1;
   };
-  for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
-    // the item's bucket: the last b with item_off[b] <= it
-    uint32_t lo_b = 0, hi_b = nb;
-    while (hi_b - lo_b > 1u) {
-      const uint32_t mid = (lo_b + hi_b) >> 1;
-      if (item_off[mid] <= it) lo_b = mid; else hi_b = mid;
+  // one bucket per thread: the thread whose bucket holds an item says so (a bucket without items holds none)
+  uint32_t my_it0 = 0, my_it1 = 0, my_e0 = 0, my_e1 = 0;
+  if (tid < nb) my_it0 = item_off[tid], my_it1 = item_off[tid + 1], my_e0 = start[tid], my_e1 = start[tid + 1];
+  auto publish = [&](uint32_t item, uint32_t slot) {
+    if (item >= my_it0 && item < my_it1) {
+      const uint32_t e_lo = my_e0 + (item - my_it0) * kFoldChunk;
+      s_item[slot][0] = tid;
+      s_item[slot][1] = my_it1 - my_it0 == 1u ? 1u : 0u;
+      s_item[slot][2] = e_lo;
+      s_item[slot][3] = my_e1 - e_lo < kFoldChunk ? my_e1 : e_lo + kFoldChunk;
     }
-    const uint32_t b = lo_b;
-    const uint32_t chunk = it - item_off[b];
-    const bool owner = item_off[b + 1] - item_off[b] == 1u;
-    // the bucket's four quarters one after the other: the chunk's entries are read four times, from the L2
-    for (uint32_t quarter = 0; quarter < kFoldQuarters; ++quarter) {
-      const uint64_t w0 = ((uint64_t)b << (kFoldBucketShift - 5)) + (uint64_t)quarter * kFoldQuarterWords;
-      if (w0 >= n_words) break;  // past the table's end: no entry can fall here
-      const uint64_t nw = n_words - w0 < kFoldQuarterWords ? n_words - w0 : kFoldQuarterWords;
+  };
+  auto item_word = [&](uint32_t slot, uint32_t k) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)s_item[slot][k]); };
+  // four 16-byte loads from the aligned-down start, without a branch: a load past the item's end is one of the 16-byte
+  // group that holds the item's last entry instead.  What lies outside the item is masked when the batch is processed
+  const uint4* g4 = reinterpret_cast<const uint4*>(grouped);
+  auto request = [&](uint4 (&d)[kIn4], uint32_t i0, uint32_t e_end) {
+    const uint32_t last = (e_end - 1u) / 4u;
+#pragma unroll
+    for (uint32_t k = 0; k < kIn4; ++k) {
+      const uint32_t i4 = i0 / 4u + k * kFoldTPB + tid;
+      d[k] = g4[i4 < last ? i4 : last];
+    }
+  };
+  publish(it, 0u);
+  fold_lds_barrier();
+  uint4 cur[kIn4], nxt[kIn4];
+  request(cur, item_word(0u, 2u) & ~3u, item_word(0u, 3u));
+  for (uint32_t slot = 0; it < n_items; it += gridDim.x, slot ^= 1u) {
+    const uint32_t b = item_word(slot, 0u);
+    const bool owner = item_word(slot, 1u) != 0u;
+    const uint32_t e_lo = item_word(slot, 2u), e_end = item_word(slot, 3u), first = e_lo & ~3u;
+    // (the other slot was last read before this item's predecessor passed its barriers; read again behind this item's)
+    const bool more = it + gridDim.x < n_items;
+    if (more) publish(it + gridDim.x, slot ^ 1u);
+    // the bucket's quarters one after the other, as far as the table reaches (no entry can fall past its end): the
+    // item's entries are read once per quarter, from the L2
+    const uint64_t wb = (uint64_t)b << (kFoldBucketShift - 5);
+    const uint64_t left = n_words - wb;
+    const uint32_t n_q = left >= (uint64_t)kFoldQuarters * kFoldQuarterWords
+                             ? kFoldQuarters : (uint32_t)((left + kFoldQuarterWords - 1u) / kFoldQuarterWords);
+    for (uint32_t quarter = 0; quarter < n_q; ++quarter) {
+      const uint64_t w0 = wb + (uint64_t)quarter * kFoldQuarterWords;
+      const uint32_t nw = n_words - w0 < kFoldQuarterWords ? (uint32_t)(n_words - w0) : kFoldQuarterWords;
       uint32_t* gw = bits + w0;
+      if (fresh && owner) {
 #pragma unroll
-      for (uint32_t k = 0; k < kPer; ++k) {
-        const uint32_t w = (k * kFoldTPB + tid) * 4u;
-        uint4 v;
-        if (fresh && owner) {
-          v = make_uint4(0u, 0u, 0u, 0u);
-        } else if (w + 4u <= nw) {
-          v = reinterpret_cast<const uint4*>(gw)[w / 4u];
-        } else {
-          v.x = w + 0u < nw ? gw[w + 0u] : 0u;
-          v.y = w + 1u < nw ? gw[w + 1u] : 0u;
-          v.z = w + 2u < nw ? gw[w + 2u] : 0u;
-          v.w = w + 3u < nw ? gw[w + 3u] : 0u;
-        }
-        q4[w / 4u] = v;
-      }
-      __syncthreads();
-      const uint32_t e_lo = start[b] + chunk * kFoldChunk;
-      const uint32_t e_end = start[b + 1] - e_lo < kFoldChunk ? start[b + 1] : e_lo + kFoldChunk;
-      // 16 entries in flight per thread (four 16-byte loads from the aligned-down start; what lies outside the chunk
-      // is skipped) before any of them is used: one round trip per 16 K entries
-      constexpr uint32_t kIn4 = 4;
-      const uint4* g4 = reinterpret_cast<const uint4*>(grouped);
-      for (uint32_t i0 = e_lo & ~3u; i0 < e_end; i0 += kIn4 * 4u * kFoldTPB) {
-        uint32_t x[kIn4 * 4];
+        for (uint32_t k = 0; k < kPer; ++k) q4[k * kFoldTPB + tid] = make_uint4(0u, 0u, 0u, 0u);
+      } else if (nw == kFoldQuarterWords) {
+        // a whole quarter: its loads together, one wait
+        uint4 v[kPer];
 #pragma unroll
-        for (uint32_t k = 0; k < kIn4; ++k) {
-          const uint32_t i = i0 + (k * kFoldTPB + tid) * 4u;
-          const uint4 v = i < e_end ? g4[i / 4u] : make_uint4(kLogNone, kLogNone, kLogNone, kLogNone);
-          x[4 * k + 0] = i + 0u >= e_lo && i + 0u < e_end ? v.x : kLogNone;
-          x[4 * k + 1] = i + 1u >= e_lo && i + 1u < e_end ? v.y : kLogNone;
-          x[4 * k + 2] = i + 2u >= e_lo && i + 2u < e_end ? v.z : kLogNone;
-          x[4 * k + 3] = i + 3u >= e_lo && i + 3u < e_end ? v.w : kLogNone;
-        }
+        for (uint32_t k = 0; k < kPer; ++k) v[k] = reinterpret_cast<const uint4*>(gw)[k * kFoldTPB + tid];
 #pragma unroll
-        for (uint32_t k = 0; k < kIn4 * 4; ++k) {
-          if (x[k] == kLogNone || ((x[k] >> kFoldQuarterShift) & (kFoldQuarters - 1u)) != quarter) continue;
-          const uint32_t m = 1u << (x[k] & 31u);
-          const uint32_t wq = (x[k] >> 5) & (kFoldQuarterWords - 1u);
-          const uint32_t old = atomicOr(&fold_smem[wq], m);
-          // a split bucket: the first of the item's entries claims the bit in memory at once; another item may have
-          // been first (a repeat after all)
-          if ((old & m) || (!owner && (atomicOr(&gw[wq], m) & m))) add(x[k]);
-        }
-      }
-      __syncthreads();
-      // the owner writes its quarter back as it is now (nearly every line of it changed for a sparse batch)
-      if (owner) {
-#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) q4[k * kFoldTPB + tid] = v[k];
+      } else {
+        // the table's ragged last quarter
+#pragma unroll 1
         for (uint32_t k = 0; k < kPer; ++k) {
           const uint32_t w = (k * kFoldTPB + tid) * 4u;
-          const uint4 cur = q4[w / 4u];
+          uint4 v;
           if (w + 4u <= nw) {
-            reinterpret_cast<uint4*>(gw)[w / 4u] = cur;
+            v = reinterpret_cast<const uint4*>(gw)[w / 4u];
           } else {
-            if (w + 0u < nw) gw[w + 0u] = cur.x;
-            if (w + 1u < nw) gw[w + 1u] = cur.y;
-            if (w + 2u < nw) gw[w + 2u] = cur.z;
+            v.x = w + 0u < nw ? gw[w + 0u] : 0u;
+            v.y = w + 1u < nw ? gw[w + 1u] : 0u;
+            v.z = w + 2u < nw ? gw[w + 2u] : 0u;
+            v.w = w + 3u < nw ? gw[w + 3u] : 0u;
+          }
+          q4[w / 4u] = v;
+        }
+      }
+      fold_lds_barrier();
+      for (uint32_t i0 = first; i0 < e_end; i0 += kBatch) {
+        if (e_end - i0 > kBatch) {
+          request(nxt, i0 + kBatch, e_end);
+        } else if (quarter + 1u < n_q) {
+          request(nxt, first, e_end);
+        } else if (more) {
+          request(nxt, item_word(slot ^ 1u, 2u) & ~3u, item_word(slot ^ 1u, 3u));
+        } else {
+#pragma unroll
+          for (uint32_t k = 0; k < kIn4; ++k) nxt[k] = none4;
+        }
+        // the batch's sixteen LDS atomics back to back, one wait: an entry of another quarter, or outside the item, ORs
+        // nothing into a word of the thread's own (no two lanes of a wave meet there)
+        const uint32_t x[kIn4 * 4] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                                      cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+        uint32_t old[kIn4 * 4], mine = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kIn4 * 4; ++k) {
+          const uint32_t i = i0 + ((k / 4u) * kFoldTPB + tid) * 4u + (k & 3u);
+          const bool on = i >= e_lo && i < e_end && ((x[k] >> kFoldQuarterShift) & (kFoldQuarters - 1u)) == quarter;
+          mine |= (on ? 1u : 0u) << k;
+          old[k] = atomicOr(&fold_smem[on ? (x[k] >> 5) & (kFoldQuarterWords - 1u) : tid], on ? 1u << (x[k] & 31u) : 0u);
+        }
+        // the two rare follow-ups, one entry at a time: a bit that was set already makes the entry a table add.  A split
+        // bucket: the first of the item's entries claims the bit in memory at once; another item may have been first (a
+        // repeat after all)
+        uint32_t again = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kIn4 * 4; ++k) again |= ((old[k] >> (x[k] & 31u)) & 1u) << k;
+        again &= mine;
+        uint32_t todo = owner ? again : mine;
+        while (todo) {
+          const uint32_t k = (uint32_t)__builtin_ctz(todo);
+          todo &= todo - 1u;
+          uint32_t v = x[0];
+#pragma unroll
+          for (uint32_t j = 1; j < kIn4 * 4; ++j) v = k == j ? x[j] : v;
+          const uint32_t m = 1u << (v & 31u);
+          if (((again >> k) & 1u) || (atomicOr(&gw[(v >> 5) & (kFoldQuarterWords - 1u)], m) & m)) add(v);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kIn4; ++k) cur[k] = nxt[k];
+      }
+      fold_lds_barrier();
+      // the owner writes its quarter back as it is now (nearly every line of it changed for a sparse batch)
+      if (owner && nw == kFoldQuarterWords) {
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) reinterpret_cast<uint4*>(gw)[k * kFoldTPB + tid] = q4[k * kFoldTPB + tid];
+      } else if (owner) {
+#pragma unroll 1
+        for (uint32_t k = 0; k < kPer; ++k) {
+          const uint32_t w = (k * kFoldTPB + tid) * 4u;
+          const uint4 c = q4[w / 4u];
+          if (w + 4u <= nw) {
+            reinterpret_cast<uint4*>(gw)[w / 4u] = c;
+          } else {
+            if (w + 0u < nw) gw[w + 0u] = c.x;
+            if (w + 1u < nw) gw[w + 1u] = c.y;
+            if (w + 2u < nw) gw[w + 2u] = c.z;
           }
         }
       }
-      __syncthreads();
+      fold_lds_barrier();
     }
   }
 }
@@ -281,11 +409,13 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
 // words in use; dirty: the table's dirty-block map, or null.  scatter_grid / apply_grid: 0 = sized from n_cus as the
 // engine does; tests force other counts to vary how tiles and items interleave.  fresh: the bit map counts as all zero
 // and is not read (see the top of the file); every one of its n_words words is written.  have_cnt: cnt already holds
-// the entries per bucket (whoever wrote the log counted them): bc_fold_hist is skipped.
+// the entries per bucket (whoever wrote the log counted them): bc_fold_hist is skipped.  log and grouped are 16-byte
+// aligned: hipErrorInvalidValue otherwise, and nothing is launched.
 inline hipError_t fold_launch(hipStream_t stream, const uint32_t* log, uint64_t n, uint32_t* grouped, uint32_t* meta,
                               uint32_t nb, uint32_t* bits, uint64_t n_words, uint32_t* table, uint8_t* dirty, uint32_t n_cus,
                               uint32_t scatter_grid = 0, uint32_t apply_grid = 0, bool fresh = false,
                               bool have_cnt = false) {
+  if ((reinterpret_cast<uintptr_t>(log) | reinterpret_cast<uintptr_t>(grouped)) & 15u) return hipErrorInvalidValue;
   uint32_t* cnt = meta;
   uint32_t* start = cnt + kFoldMaxBuckets + 1;
   uint32_t* cursor = start + kFoldMaxBuckets + 1;
