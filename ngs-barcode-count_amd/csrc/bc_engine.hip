@@ -928,7 +928,7 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     const int rc = settle_bits_on(e, e->stream);
     if (rc != BC_OK) return rc;
   }
-  const uint32_t flags = (e->pipe ? 1u : 0u) | (s.tables_generic ? 2u : 0u) | (s.hot_generic && hot_on ? 4u : 0u);
+  const uint32_t flags = (s.pipe ? 1u : 0u) | (s.tables_generic ? 2u : 0u) | (s.hot_generic && hot_on ? 4u : 0u);
   if (s.lds + 64 > e->lds_limit) {
     set_error("read stride too large for one LDS tile");
     return BC_ERR_UNSUPPORTED;
@@ -992,7 +992,7 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     if (jit_fn) {
       uint32_t a_region = s.region;
       uint64_t a_smask = e->n_slots ? e->n_slots - 1 : 0;
-      uint32_t a_flags = (e->pipe ? 1u : 0u) | (s.tables_jit ? 2u : 0u) | (s.hot_jit && hot_on ? 4u : 0u);
+      uint32_t a_flags = (s.pipe ? 1u : 0u) | (s.tables_jit ? 2u : 0u) | (s.hot_jit && hot_on ? 4u : 0u);
       void* args[] = {&a_seq, &a_qual, &a_lens, &a_qlens, &stride, &read_len, &nd, &a_n, &a_region, &e->d_table, &e->d_bits, &e->d_slots,
                       &e->d_vals, &a_smask, &e->d_counters, &a_to, &a_ti, &a_flags, &a_log};
       const uint64_t grid = std::min<uint64_t>(blocks_jit, (n_c + kTPB - 1) / kTPB);
@@ -1163,8 +1163,14 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
   }
   // plans or reads beyond the lane-per-read kernel's widths: the wave-per-read kernel (bc_long.h)
   if (e->long_only || maxlen > 320u) return launch_long(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads, trace_off);
-  const MatchShape s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr,
-                                   e->lds_limit, e->pipe, e->qshare, e->lhash_mode);
+  MatchShape s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr,
+                             e->lds_limit, e->pipe, e->qshare, e->lhash_mode);
+  // With the quality filter on, the pipelined fetch keeps two tile regions per wave: from 315 bases on (four waves x
+  // two regions of 64 x 315 bytes and their slack) they no longer fit the LDS.  Such a batch is fetched on demand
+  // into one region per wave -- the path every partial tile takes -- instead of being refused.
+  if (s.pipe && s.lds + 64 > e->lds_limit)
+    s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr, e->lds_limit, false,
+                    e->qshare, e->lhash_mode);
   const int nww = s.jit.NWW;  // words of candidate offsets: the exact count; the instantiations round it up
 #define BC_LAUNCH(NW_, NWW_) \
   return launch_match<NW_, NWW_>(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, nd, n_reads, trace_off, s)

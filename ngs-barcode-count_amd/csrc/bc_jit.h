@@ -46,6 +46,7 @@ struct MatchShape {
   uint32_t lds_cold, lds_jit_cold;  // ... of a launch with the hot-counter cache off (the same where a plan has none)
   bool tables_generic, tables_jit;  // LDS exact-match tables
   bool hot_generic, hot_jit;        // hot-counter cache (log mode may still switch it off per launch: lds_cold)
+  bool pipe;                        // the tile fetch the LDS figures are for: software-pipelined, or on demand
   JitShape jit;
   int first_min_waves;              // waves per SIMD the specialised build tries first
   uint64_t key;                     // the engine's key for the specialised kernel of this shape

@@ -58,13 +58,25 @@ def make_plan(case, variant="generic"):
     return p
 
 
-def emulate(plan, seq, qual, lens, stride, read_len, with_random=False, qlens=None):
-    """-> (outcomes, dense idx, table entries, discard flag); with_random adds (rcode, rspace): in
-    random-barcode mode outcome 0 means "passed every test" -- set membership is the caller's job"""
-    L = plan._lib  # the emu variant the plan was made with
+def open_plan(plan):
+    """the emulation's lowered form of `plan`, for several emulate(handle=) calls; close_plan() frees it"""
+    L = plan._lib
     e = L.emu_plan_create(plan._p)
     if not e:
         raise RuntimeError(L.bc_last_error().decode())
+    return e
+
+
+def close_plan(plan, handle):
+    plan._lib.emu_plan_destroy(handle)
+
+
+def emulate(plan, seq, qual, lens, stride, read_len, with_random=False, qlens=None, handle=None):
+    """-> (outcomes, dense idx, table entries, discard flag); with_random adds (rcode, rspace): in
+    random-barcode mode outcome 0 means "passed every test" -- set membership is the caller's job.
+    handle: open_plan(plan), lowered once for many batches (default: lowered here, for this batch)"""
+    L = plan._lib  # the emu variant the plan was made with
+    e = handle or open_plan(plan)
     n = seq.size // stride
     outc = np.zeros(n, dtype=np.uint8)
     idx = np.zeros(n, dtype=np.uint64)
@@ -75,7 +87,8 @@ def emulate(plan, seq, qual, lens, stride, read_len, with_random=False, qlens=No
     entries = L.emu_table_entries(e)
     discard = L.emu_discard_counts(e)
     rspace = L.emu_rspace(e)
-    L.emu_plan_destroy(e)
+    if not handle:
+        L.emu_plan_destroy(e)
     assert rc == 0
     if with_random:
         return outc, idx, entries, discard, rcode, rspace

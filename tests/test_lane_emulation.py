@@ -9,6 +9,7 @@ import cases
 import emu_lib
 import parity
 import readgen
+import seam_cases
 
 NO_RANDOM = cases.NO_RANDOM_CASES
 
@@ -85,6 +86,34 @@ def test_long_reads_use_wider_planes(variant):
         seq, qual, lens = readgen.to_arrays(c["reads"])
         outc, idx, entries, discard = emu_lib.emulate(plan, seq.reshape(-1), qual.reshape(-1), None, rl, rl)
         parity.check_per_read(c, plan, outc, idx, discard)
+
+
+@pytest.mark.parametrize("which", sorted(seam_cases.SWEEP_CASES))
+@pytest.mark.parametrize("use_lens", [False, True], ids=["fixed", "ragged"])
+def test_length_sweep_across_the_dispatch_edges(which, use_lens):
+    """every read length from the scheme's own to 320 that is within one base of a multiple of 32 (the plane words) or
+    within two of L + 32 k (the words of candidate offsets), fixed and ragged, both variants: the lane code's side of the
+    edges at which the engine changes kernel (tests/test_gpu_kernel_seams.py runs them on the device)"""
+    c = seam_cases.SWEEP_CASES[which]()
+    plans = [emu_lib.make_plan(c, variant) for variant in VARIANTS]
+    lengths = seam_cases.sweep_lengths(seam_cases.SWEEP_L[which])
+    assert plans[0].length == lengths[0] and lengths[-1] == 320 and {160, 161, 256, 257}.issubset(lengths)
+    handles = [emu_lib.open_plan(plan) for plan in plans]  # (lowered once: the sweep runs some sixty batches each)
+    matched = 0
+    try:
+        for m in lengths:
+            b = seam_cases.shape_batch(which, m, use_lens, n=400, keep=False)
+            for variant, plan, handle in zip(VARIANTS, plans, handles):
+                outc, idx, entries, discard = emu_lib.emulate(plan, b["seq"], b["qual"], b["lens"], m, m, handle=handle)
+                try:
+                    o = parity.check_per_read(dict(c, reads=b["reads"]), plan, outc, idx, discard)
+                except AssertionError as ex:
+                    raise AssertionError("length %d, %s" % (m, variant)) from ex
+                matched += o.counters["matched"]
+    finally:
+        for plan, handle in zip(plans, handles):
+            emu_lib.close_plan(plan, handle)
+    assert matched > 100 * len(lengths)
 
 
 def test_plan_matches_oracle_scheme_compile():
