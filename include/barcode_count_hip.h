@@ -309,6 +309,46 @@ int bc_engine_wide_render_sorts(const bc_engine *e, uint64_t *n);
  * before any. */
 int bc_engine_wide_render_sort_ms(const bc_engine *e, double *ms);
 
+/* The Single and Double enrichment files of a raw-key plan (bc_plan_mode 2, one-word keys) as CSV text, written on the
+ * device: what bc_engine_render_enriched / _merged are to a dense plan.  `kind` is BC_ENRICH_SINGLE or BC_ENRICH_DOUBLE.
+ * The sums are made from the sorted rows of bc_engine_render_raw_counts (the same sort is shared; nothing else is exported
+ * from the map): per counted barcode g (Single) or pair g < h (Double, in add_double's order (0,1), (0,2), .., (1,2), ..)
+ * every row is projected to the key  d_g * S + s  or  (d_g * R_h + d_h) * S + s  (d: the digit bc_engine_render_raw_counts
+ * orders by -- the set index of a known barcode, sum_k c_k * 5^k of a raw one; R_h: barcode h's radix; s: the sample index
+ * of S), the projected keys are sorted over their own bit length and every run of equal keys is reduced to its u64 sum,
+ * all on the device.  Entries of one known set whose IDs are byte-equal are ONE key, as in the dense call: their digit is
+ * the smallest index with that ID.  Text that coincides across DIFFERENT barcodes or pairs -- possible only when some ID is
+ * empty -- is NOT merged.
+ * A line has G fields joined by commas, as add_single / add_double build the key (info.rs:840-904): field g (and h) holds
+ * the ID of a known barcode, copied byte for byte, or the bases of a raw capture as they were read; every other field is
+ * empty; then the sum(s), u64 in decimal.  Three raw barcodes of 8 bases:
+ *   ,ACGTACGT,,7\n           Single of barcode 2          ACGTACGT,,TTGCAAGC,3\n   Double of barcodes 1 and 3
+ *   bc_engine_render_raw_enriched: one line per key that sample_idx counts.
+ *   bc_engine_render_raw_enriched_merged: one line per key whose sum is not zero for some LISTED sample, one sum per listed
+ *     sample (any order, a sample may come twice), 0 written as "0".
+ * Order: Single lines ascend by (g, d_g), Double lines by (pair, d_g, d_h); the text is the same on every run.  No header.
+ * BC_ENRICH_DOUBLE with fewer than three counted barcodes, and an engine nothing was submitted to: no line, BC_OK.
+ * Each kind is built once per state of the counts, at its first render, and kept on the device -- 16 bytes per (key,
+ * sample) that counts, plus the segment starts -- until the sorted rows are retired (a submit, a reset, a key or count
+ * import, bc_engine_clear_keys, the exchange of bc_engine_finish_all).  While a kind is built: 32.5 bytes per row
+ * beside the sorted rows (one set of buffers that every projection uses in turn), released before the render.  On the root after bc_engine_finish_all the calls render the job's
+ * merged map.
+ * Chunking, BC_RENDER_CHUNK_BYTES, the callback contract (`fn` != 0 -> BC_ERR_STATE, the engine still usable) and
+ * BC_ERR_NOMEM (everything taken is released) are those of bc_engine_render_raw_counts.
+ * BC_ERR_UNSUPPORTED: a dense plan (use bc_engine_render_enriched / _merged); a plan with wide keys
+ * (bc_engine_key_words() > 1) or whose SAMPLE barcode is kept raw -- build those files from bc_engine_finish +
+ * bc_engine_row_text on the host.  BC_ERR_INVALID: another kind, a sample index out of range, a null callback, a null
+ * list with n_samples != 0. */
+int bc_engine_render_raw_enriched(bc_engine *e, int kind, uint32_t sample_idx, bc_text_fn fn, void *user, uint64_t *n_rows);
+int bc_engine_render_raw_enriched_merged(bc_engine *e, int kind, const uint32_t *sample_idx, uint32_t n_samples,
+                                         bc_text_fn fn, void *user, uint64_t *n_rows);
+/* How many kinds the engine has built for those renders since it was created (+1 for the Single set, +1 for the Double
+ * set, per state of the counts).  Read-only: does not wait for the device. */
+int bc_engine_raw_enrich_reduces(const bc_engine *e, uint64_t *n);
+/* Device time of the last build (every projection of one kind: project, sort, reduce, join), in milliseconds, from HIP
+ * events; 0 before any. */
+int bc_engine_raw_enrich_reduce_ms(const bc_engine *e, double *ms);
+
 /* Row i as the reference's Results holds it (info.rs:661-665): the sample key (a sample barcode
  * sequence, or "barcode" without a sample group) and the counted barcodes "b1,b2,.." as sequences.
  * Works for every plan, including those that keep raw captures (no sample / counted-barcode

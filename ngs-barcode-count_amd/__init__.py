@@ -407,6 +407,35 @@ class Engine:
         return self._render(lambda fn, n: self._lib.bc_engine_render_enriched_merged(
             self._e, int(kind), cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
 
+    def render_raw_enriched(self, kind, sample=0, on_text=None):
+        """bc_engine_render_raw_enriched: render_enriched() for a raw-key plan: the lines of sample index `sample`'s Single
+        (kind = ENRICH_SINGLE) or Double (ENRICH_DOUBLE) file (no header), summed, sorted and written on the device.  A
+        field holds the ID of a known barcode or the bases of a raw capture, e.g. b",ACGTACGT,,7\\n"; Single lines ascend
+        by (barcode, digit), Double lines by (pair, digit, digit), the digits being render_raw_counts()'s.  Returns as
+        render_counts does."""
+        return self._render(lambda fn, n: self._lib.bc_engine_render_raw_enriched(self._e, int(kind), int(sample), fn, None, n),
+                            on_text)
+
+    def render_raw_enriched_merged(self, kind, samples, on_text=None):
+        """bc_engine_render_raw_enriched_merged: the merged Single / Double file's lines (no header) of a raw-key plan for
+        the sample indices `samples` as columns, in that order: one line per key that counts in any LISTED sample."""
+        cols = np.ascontiguousarray(list(samples), dtype=np.uint32)
+        return self._render(lambda fn, n: self._lib.bc_engine_render_raw_enriched_merged(
+            self._e, int(kind), cols.ctypes.data if cols.size else None, cols.size, fn, None, n), on_text)
+
+    def raw_enrich_reduces(self):
+        """kinds (Single, Double) built for render_raw_enriched() / render_raw_enriched_merged() since the engine was
+        created: the renders of one state of the counts share one build per kind"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_raw_enrich_reduces(self._e, C.byref(n)))
+        return n.value
+
+    def raw_enrich_reduce_ms(self):
+        """device milliseconds of the last of those builds (project, sort, reduce of every projection of one kind)"""
+        v = C.c_double()
+        _check(self._lib, self._lib.bc_engine_raw_enrich_reduce_ms(self._e, C.byref(v)))
+        return v.value
+
     def enrichment(self, doubles=True):
         """bc_engine_enrich: single and pair counts of the counts finish() would hand out now, summed on the device ->
         (singles, doubles): singles = [uint64 array (S, N_g) per counted barcode g]; doubles = {(g, h): uint64 array

@@ -105,6 +105,10 @@ ENGINE_API = {
     "bc_engine_render_enriched_merged": (_int, [_vp, _int, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "bc_engine_render_raw_counts": (_int, [_vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     "bc_engine_render_raw_merged": (_int, [_vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_render_raw_enriched": (_int, [_vp, _int, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_render_raw_enriched_merged": (_int, [_vp, _int, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
+    "bc_engine_raw_enrich_reduces": (_int, [_vp, C.POINTER(C.c_uint64)]),
+    "bc_engine_raw_enrich_reduce_ms": (_int, [_vp, C.POINTER(C.c_double)]),
     "bc_engine_raw_render_sorts": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_engine_raw_render_sort_ms": (_int, [_vp, C.POINTER(C.c_double)]),
     "bc_engine_render_wide_counts": (_int, [_vp, _u32, _vp, _vp, C.POINTER(_u64)]),

@@ -286,6 +286,9 @@ struct Run {
   // a raw-key plan's full-counts files sorted and written on the device (bc_engine_render_raw_counts / _merged;
   // BC_DEVICE_RAW_WRITERS=1): no rows on the host either
   bool raw_writers = false;
+  // ... and its Single / Double files (bc_engine_render_raw_enriched / _merged; BC_DEVICE_RAW_ENRICH_WRITERS=1 on top):
+  // device_enrich is set with it, so nothing below builds single_hash / double_hash
+  bool raw_enrich = false;
   bool wide_keys = false;  // ... through bc_engine_render_wide_counts / _merged: the plan's keys are several words wide
   std::unordered_map<std::string, uint32_t> sample_index;  // sample key -> the engine's sample index
 };
@@ -555,7 +558,10 @@ uint64_t render_file(Run& r, const std::string& name, const std::string& head, c
   if (fwrite(head.data(), 1, head.size(), f) != head.size()) die("%s: write failed", path.c_str());
   uint64_t n = 0;
   int rc;
-  if (enriched)
+  if (enriched && r.raw_enrich)
+    rc = merged ? bc_engine_render_raw_enriched_merged(r.engine, enriched, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
+                : bc_engine_render_raw_enriched(r.engine, enriched, cols[0], text_to_file, f, &n);
+  else if (enriched)
     rc = merged ? bc_engine_render_enriched_merged(r.engine, enriched, cols.data(), (uint32_t)cols.size(), text_to_file, f, &n)
                 : bc_engine_render_enriched(r.engine, enriched, cols[0], text_to_file, f, &n);
   else if (r.raw_writers && r.wide_keys)
@@ -577,7 +583,8 @@ void print_rows_progress(uint64_t n) {
   printf("Barcodes counted: %s\r\n", commas(n).c_str());
 }
 // The device path of the Single / Double files: a key is an index into the device's marginal sums, its line a function
-// of that index (bc_engine_render_enriched).  Every sample key has a file, as every key has a map on the host path
+// of that index (bc_engine_render_enriched; for a raw-key plan a position in the device's sorted sums,
+// bc_engine_render_raw_enriched).  Every sample key has a file, as every key has a map on the host path
 // (add_sample_barcodes); file names, headers, stdout and output_counts are those of write_enriched_files below.
 void render_enriched_files(Run& r, Enriched type) {
   const auto samples = ordered_samples(r, r.sample_keys);
@@ -952,16 +959,26 @@ int main(int argc, char** argv) {
   // Raw-key plans (some counted barcode has no conversion file): with BC_DEVICE_RAW_WRITERS=1 the full-counts files are
   // sorted and rendered on the device from the key map (bc_engine_render_raw_counts / _merged, or, for keys several
   // words wide, bc_engine_render_wide_counts / _merged), which may change the order of the lines in those files and
-  // nothing else.  Kept on the rows: a sample barcode kept raw (its samples are captures), enrichment (it needs the rows' strings), a counted file that names only some of the
-  // barcodes, and a sample file next to a scheme without a sample group (as above).
+  // nothing else.  Kept on the rows: a sample barcode kept raw (its samples are captures), a counted file that names only
+  // some of the barcodes, a sample file next to a scheme without a sample group (as above), and enrichment -- unless
+  // BC_DEVICE_RAW_ENRICH_WRITERS=1 is set as well and the keys are one word wide: the Single / Double files then come
+  // from the device too (bc_engine_render_raw_enriched / _merged; sums made by a sort and a run reduction of the sorted
+  // key map), which again may change the order of their lines and nothing else.
   const bool raw_plan = bc_plan_mode(r.plan) == 2;
   if (raw_plan) {
     const char* rw = getenv("BC_DEVICE_RAW_WRITERS");
     bool counted_whole = true;  // the counted file is absent, or names every counted barcode
     for (const auto& set : r.counted) counted_whole = counted_whole && !set.empty();
     r.wide_keys = bc_engine_key_words(r.engine) > 1;
+    const char* re = getenv("BC_DEVICE_RAW_ENRICH_WRITERS");
+    // (No test of the IDs is needed here, unlike for dense plans.  A plan with one-word keys is a raw-key plan only when
+    // some group has no known set; with the sample barcode known or absent that group is a counted one, so the counted
+    // file does not name every barcode, and `counted_whole` then holds only when there is no counted file at all: on
+    // this path r.counted is empty and every field is a capture, never an ID.)
+    const bool raw_enrich_ok = re && strcmp(re, "1") == 0 && !r.wide_keys;
     r.raw_writers = rw && strcmp(rw, "1") == 0 && (!sample_group || !r.samples.empty()) && (sample_group || r.samples.empty()) &&
-                    !r.args.enrich && counted_whole;
+                    (!r.args.enrich || raw_enrich_ok) && counted_whole;
+    r.raw_enrich = r.device_enrich = r.raw_writers && r.args.enrich;
     if (r.raw_writers) {
       if (sample_group)
         for (uint32_t i = 0; i < r.samples.size(); ++i) r.sample_index[r.samples[i].first] = i;
@@ -975,7 +992,8 @@ int main(int argc, char** argv) {
             r.device_writers ? "device text (bc_engine_render_counts)" : "per-row strings");
   if (r.args.enrich && getenv("BC_WRITERS_VERBOSE"))  // (... and the Single / Double files)
     fprintf(stderr, "[barcode-count] enrichment writers: %s\n",
-            r.device_enrich ? "device text (bc_engine_render_enriched)" : "per-row strings");
+            r.raw_enrich ? "device text (bc_engine_render_raw_enriched)"
+                         : (r.device_enrich ? "device text (bc_engine_render_enriched)" : "per-row strings"));
   if (raw_plan && getenv("BC_WRITERS_VERBOSE"))  // (... of a raw-key plan)
     fprintf(stderr, "[barcode-count] raw writers: %s\n",
             !r.raw_writers ? "per-row strings"
@@ -1032,7 +1050,8 @@ int main(int argc, char** argv) {
     fill_enrichment(r, sample_group);
   if (r.args.enrich && getenv("BC_ENRICH_VERBOSE"))  // (which path built the Single / Double maps; tests assert it)
     fprintf(stderr, "[barcode-count] enrichment: %s\n",
-            r.device_enrich ? "device marginal sums (bc_engine_render_enriched)"
+            r.raw_enrich ? "device run sums (bc_engine_render_raw_enriched)"
+            : r.device_enrich ? "device marginal sums (bc_engine_render_enriched)"
                             : (r.enrich_filled ? "device marginal sums (bc_engine_enrich)" : "per-row string adds"));
   write_counts_files(r);
   if (r.args.enrich && getenv("BC_ENRICH_VERBOSE")) {  // (the device path of the Single / Double files builds none)

@@ -561,6 +561,8 @@ static void engine_free(bc_engine* e) {
   if (e->d_ready) (void)hipFree(e->d_ready);
   if (e->d_sums) (void)hipFree(e->d_sums);
   if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
+  for (void* p : e->d_re)
+    if (p) (void)hipFree(p);
   if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
   if (e->d_wide_keys) (void)hipFree(e->d_wide_keys);
   if (e->d_wide_cnts) (void)hipFree(e->d_wide_cnts);

@@ -179,6 +179,16 @@ struct bc_engine {
   uint64_t raw_n = 0;
   uint64_t raw_sorts = 0;                // sorts made since the engine was created (bc_engine_raw_render_sorts)
   float raw_sort_ms = 0.f;               // export + re-key + sort of the last one, from HIP events
+  // The raw-key enrichment renderer (bc_raw_enrich_render.h): per kind ([0] Single, [1] Double) the (projected key, sum)
+  // segments made from the sorted pairs above (project, bc_sort.h, bc_reduce.h), in one allocation -- re_n keys, re_n
+  // sums, re_segs + 1 segment starts, u64 all -- built at the kind's first render of a counts epoch and retired with the
+  // sorted pairs.
+  uint64_t re_epoch[2] = {0, 0};
+  void* d_re[2] = {nullptr, nullptr};
+  uint64_t re_n[2] = {0, 0};
+  uint32_t re_segs[2] = {0, 0};
+  uint64_t raw_enrich_builds = 0;        // kinds built since the engine was created (bc_engine_raw_enrich_reduces)
+  float raw_enrich_ms = 0.f;             // project + sort + reduce of the last one, from HIP events
   // The wide-key renderer (bc_wide_render.h): the exported keys (key_words u64 each) and counts gathered into the order
   // of the files, kept on the device under the counts epoch exactly as d_raw_keys is.
   uint64_t wide_epoch = 0;

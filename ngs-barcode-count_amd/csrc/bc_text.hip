@@ -2,8 +2,9 @@
 // (bc_engine_render_counts / _merged; lane code bc_render.h), the Single and Double enrichment files
 // (bc_engine_render_enriched / _merged; bc_enrich_render.h) and the sorted counts files of a raw-key plan
 // (bc_engine_render_raw_counts / _merged; bc_raw_render.h, bc_sort.h) and of a wide-key plan
-// (bc_engine_render_wide_counts / _merged; bc_wide_render.h, bc_sort.h).  A renderer is a view struct with lane code and a
-// front end that checks the request and fills the view; the kernels (bc_text_kernels.h) and the host loop around them
+// (bc_engine_render_wide_counts / _merged; bc_wide_render.h, bc_sort.h), and the Single and Double files of a raw-key
+// plan (bc_engine_render_raw_enriched / _merged; bc_raw_enrich_render.h, bc_sort.h, bc_reduce.h).  A renderer is a view
+// struct with lane code and a front end that checks the request and fills the view; the kernels (bc_text_kernels.h) and the host loop around them
 // (stream_text) are templates over the view.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -16,7 +17,9 @@
 
 #include "bc_engine_impl.h"
 #include "bc_enrich_render.h"
+#include "bc_raw_enrich_render.h"
 #include "bc_raw_render.h"
+#include "bc_reduce.h"
 #include "bc_sort.h"
 #include "bc_text_kernels.h"
 #include "bc_wide_render.h"
@@ -339,7 +342,18 @@ static hipError_t raw_rekey_launch(uint64_t* d_keys, uint64_t n, uint64_t t_spac
   return hipGetLastError();
 }
 
+// the sums of one kind of a raw-key plan's enrichment (k = 0: Single, 1: Double; ensure_raw_enrich below)
+static void raw_enrich_drop(bc_engine* e, int k) {
+  if (e->d_re[k]) (void)hipFree(e->d_re[k]);
+  e->d_re[k] = nullptr;
+  e->re_n[k] = 0;
+  e->re_segs[k] = 0;
+  e->re_epoch[k] = 0;
+}
+
 static void raw_sorted_drop(bc_engine* e) {
+  raw_enrich_drop(e, 0);  // (made from the sorted pairs: they go together)
+  raw_enrich_drop(e, 1);
   if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
   if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
   e->d_raw_keys = nullptr;
@@ -876,6 +890,253 @@ int bc_engine_render_enriched_merged(bc_engine* e, int kind, const uint32_t* sam
 
 int bc_engine_enrich_render_passes(const bc_engine* e, uint64_t* n) {
   *n = e->sums_passes;
+  return BC_OK;
+}
+
+}  // extern "C"
+
+// ---- Single / Double enrichment of a raw-key plan as text (bc_raw_enrich_render.h, bc_sort.h, bc_reduce.h) ----
+
+namespace bc {
+
+// out_keys[i] = the projection of keys[i], out_vals[i] = cnts[i]: one lane per entry
+__global__ __launch_bounds__(256) void raw_enrich_project_kernel(RawEnrichProj p, const unsigned long long* __restrict__ keys,
+                                                                 const uint32_t* __restrict__ cnts, uint64_t n,
+                                                                 unsigned long long* __restrict__ out_keys,
+                                                                 uint32_t* __restrict__ out_vals) {
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+    out_keys[i] = raw_enrich_project(p, keys[i]);
+    out_vals[i] = cnts[i];
+  }
+}
+
+}  // namespace bc
+
+// The (projected key, sum) segments of one kind (k = 0: Single, 1: Double) for the sorted pairs as they stand
+// (ensure_raw_sorted has run, e->raw_n != 0), in e->d_re[k]: served as they are while the counts epoch stands, else
+// made projection by projection -- project, sort over the bits of the projection's bound, reduce the runs, keep the
+// runs in an allocation of their own size -- and joined at the end.  Every projection is sorted, the Single of group 0
+// too: its input ascends in d_0 already, but entries of one (d_0, s) are not adjacent there (s is the least significant
+// digit of every key in between), and a reduction needs them adjacent.
+// Device memory while a kind is built, n = raw_n: 12 n (projected pairs) + 12 n (the sort's other buffers, whose keys
+// then take the runs' keys) + n / 2 (histograms) + 8 n (sums) = 32.5 n bytes beside the kept 12 n -- one set of buffers,
+// allocated once and used by every projection in turn (the stream orders the reuse), released before the segments are
+// joined; kept: 16 bytes per (key, sample) with a sum, twice that while the segments are joined.
+static int ensure_raw_enrich(bc_engine* e, int k, const bc::RawEnrichProj& base) {
+  if (e->re_epoch[k] == e->counts_epoch) return BC_OK;
+  raw_enrich_drop(e, k);
+  const uint64_t n = e->raw_n;
+  const uint32_t G = base.G, n_seg = k == 0 ? G : G * (G - 1u) / 2u;
+  ScratchGuard segs;  // every projection's runs (keys, then sums) until they are joined
+  std::vector<uint64_t> start;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIP_TRY(hipEventCreate(&ev0));
+  segs.events.push_back(ev0);
+  HIP_TRY(hipEventCreate(&ev1));
+  segs.events.push_back(ev1);
+  HIP_TRY(hipEventRecord(ev0, e->stream));
+  try {
+    start.reserve(n_seg + 1u);
+    segs.dev.reserve(2u * n_seg + 2u);
+  } catch (const std::bad_alloc&) {
+    set_error("raw enrichment: out of host memory");
+    return BC_ERR_NOMEM;
+  }
+  uint64_t total = 0;
+  {
+    ScratchGuard s;  // the buffers every projection works in: gone before the segments are joined
+    uint64_t *d_pk = nullptr, *d_tk = nullptr, *d_sum = nullptr;
+    uint32_t *d_pv = nullptr, *d_tv = nullptr, *d_sort = nullptr, *d_red = nullptr, *d_runs = nullptr;
+    HIP_TRY(s.dmalloc(&d_pk, n * 8));
+    HIP_TRY(s.dmalloc(&d_pv, n * 4));
+    HIP_TRY(s.dmalloc(&d_tk, n * 8));
+    HIP_TRY(s.dmalloc(&d_tv, n * 4));
+    HIP_TRY(s.dmalloc(&d_sort, bc::sort_scratch_words(n) * 4));
+    HIP_TRY(s.dmalloc(&d_sum, n * 8));
+    HIP_TRY(s.dmalloc(&d_red, bc::reduce_scratch_words(n) * 4));
+    HIP_TRY(s.dmalloc(&d_runs, 4));
+    for (uint32_t g = 0; g < G; ++g)
+      for (uint32_t h = k == 0 ? g : g + 1u; h < (k == 0 ? g + 1u : G); ++h) {
+        bc::RawEnrichProj p = base;
+        p.g = g;
+        p.h = h;
+        const uint64_t bound = bc::raw_enrich_bound(p);
+        uint32_t key_bits = 1;
+        while (key_bits < 64 && ((bound - 1u) >> key_bits) != 0) ++key_bits;
+        hipLaunchKernelGGL(raw_enrich_project_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, p,
+                           (const unsigned long long*)e->d_raw_keys, (const uint32_t*)e->d_raw_cnts, n, (unsigned long long*)d_pk, d_pv);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(bc::sort_pairs_launch(e->stream, d_pk, d_pv, d_tk, d_tv, n, key_bits, d_sort));
+        HIP_TRY(bc::reduce_runs_launch(e->stream, d_pk, d_pv, n, d_tk, d_sum, d_runs, d_red));
+        uint32_t runs = 0;
+        HIP_TRY(hipMemcpyAsync(&runs, d_runs, 4, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));  // (the one wait of a projection beside the sort's own)
+        if (runs > n) {  // (cannot happen: there are no more runs than pairs)
+          set_error("raw enrichment: the reduction reports more runs than pairs");
+          return BC_ERR_STATE;
+        }
+        uint64_t *d_rk = nullptr, *d_rs = nullptr;
+        HIP_TRY(segs.dmalloc(&d_rk, (size_t)runs * 8));
+        HIP_TRY(segs.dmalloc(&d_rs, (size_t)runs * 8));
+        if (runs) {  // (the next projection's kernels come after these copies on the stream)
+          HIP_TRY(hipMemcpyAsync(d_rk, d_tk, (size_t)runs * 8, hipMemcpyDeviceToDevice, e->stream));
+          HIP_TRY(hipMemcpyAsync(d_rs, d_sum, (size_t)runs * 8, hipMemcpyDeviceToDevice, e->stream));
+        }
+        start.push_back(total);
+        total += runs;
+      }
+    HIP_TRY(hipStreamSynchronize(e->stream));  // nothing may still read the buffers when they go
+  }
+  start.push_back(total);
+  // keys, sums, segment starts: one allocation
+  void* d_all = nullptr;
+  HIP_TRY(hipMalloc(&d_all, (size_t)(2u * total + n_seg + 1u) * 8));
+  uint64_t* d_keys = (uint64_t*)d_all;
+  uint64_t* d_sums = d_keys + total;
+  auto join = [&]() -> int {
+    for (uint32_t q = 0; q < n_seg; ++q) {
+      const uint64_t len = start[q + 1u] - start[q];
+      if (!len) continue;
+      HIP_TRY(hipMemcpyAsync(d_keys + start[q], segs.dev[2u * q], (size_t)len * 8, hipMemcpyDeviceToDevice, e->stream));
+      HIP_TRY(hipMemcpyAsync(d_sums + start[q], segs.dev[2u * q + 1u], (size_t)len * 8, hipMemcpyDeviceToDevice, e->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(d_sums + total, start.data(), (size_t)(n_seg + 1u) * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(ev1, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return BC_OK;
+  };
+  const int rc = join();
+  if (rc != BC_OK) {
+    (void)hipFree(d_all);
+    return rc;
+  }
+  (void)hipEventElapsedTime(&e->raw_enrich_ms, ev0, ev1);
+  e->d_re[k] = d_all;
+  e->re_n[k] = total;
+  e->re_segs[k] = n_seg;
+  e->re_epoch[k] = e->counts_epoch;
+  ++e->raw_enrich_builds;
+  return BC_OK;
+}
+
+static int render_raw_enriched(bc_engine* e, const char* who, bool merged, int kind, const uint32_t* cols, uint32_t n_cols,
+                               bc_text_fn fn, void* user, uint64_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  const DevPlan& P = e->h.plan;
+  if (!P.sparse) {
+    set_error(std::string(who) + ": the plan has a dense table: its Single / Double files come from "
+              "bc_engine_render_enriched / bc_engine_render_enriched_merged");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->key_words > 1) {
+    set_error(std::string(who) + ": the plan's keys are " + std::to_string(e->key_words) +
+              " words wide; build its Single / Double files from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
+    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: build the "
+              "Single / Double files from bc_engine_finish + bc_engine_row_text on the host");
+    return BC_ERR_UNSUPPORTED;
+  }
+  if (kind != BC_ENRICH_SINGLE && kind != BC_ENRICH_DOUBLE) {
+    set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
+    return BC_ERR_INVALID;
+  }
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  const uint32_t S = g0 ? P.groups[0].n_refs : 1u;
+  const uint64_t t_space = g0 ? P.groups[0].table_stride : e->h.table_entries;
+  int rc = check_request(who, cols, n_cols, fn, S);
+  if (rc) return rc;
+  const uint32_t G = e->barcode_num;
+  if (G > (uint32_t)bc::kRenderMaxG || g0 + G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
+    set_error(std::string(who) + ": the plan's groups do not fit the view");
+    return BC_ERR_STATE;
+  }
+  if (kind == BC_ENRICH_DOUBLE && G < 3) return BC_OK;  // (no pairs below three counted barcodes, as the dense call)
+  HIP_TRY(hipSetDevice(e->device));
+  if ((rc = bc_engine_sync(e)) != BC_OK) return rc;  // the submits, as bc_engine_finish waits for them
+  if ((rc = ensure_raw_sorted(e, t_space, S)) != BC_OK) return rc;
+  if (n_cols == 0 || e->raw_n == 0 || G == 0) return BC_OK;
+  if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
+  if ((rc = ensure_canon(e, who)) != BC_OK) return rc;
+  bc::RawEnrichProj proj;
+  bc::RawEnrichView v;
+  memset(&proj, 0, sizeof proj);
+  memset(&v, 0, sizeof v);
+  proj.canon = e->d_canon;
+  proj.S = v.S = S;
+  proj.G = v.G = G;
+  v.kind = (uint32_t)kind;
+  v.merged = merged ? 1u : 0u;
+  v.sample = n_cols ? cols[0] : 0u;
+  v.n_cols = n_cols;
+  uint32_t longest[2] = {0, 0};  // the two longest fields of different groups
+  uint32_t canon_off = 0;
+  for (uint32_t g = 0; g < G; ++g) {
+    const DevGroup& Gr = P.groups[g0 + g];
+    uint32_t m;
+    proj.canon_off[g] = canon_off;
+    if (Gr.mode == kSetNone) {
+      v.raw_len[g] = m = Gr.len;
+      v.radix[g] = 1;
+      for (uint32_t b = 0; b < Gr.len; ++b) v.radix[g] *= 5;
+    } else {
+      if (bc_plan_n_counted(e->src_plan, g) != Gr.n_refs) {  // (cannot happen: the key's digits are the plan's sets)
+        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+        return BC_ERR_STATE;
+      }
+      proj.known[g] = 1u;
+      v.radix[g] = Gr.n_refs;
+      v.off_start[g] = e->label_off_start[g];
+      m = e->label_max[g];
+    }
+    proj.radix[g] = v.radix[g];
+    canon_off += bc_plan_n_counted(e->src_plan, g);  // (ensure_canon lays the sets out back to back)
+    if (m > longest[0]) {
+      longest[1] = longest[0];
+      longest[0] = m;
+    } else if (m > longest[1]) {
+      longest[1] = m;
+    }
+  }
+  const uint64_t max_line = 1 + (G - 1) + 21ull * n_cols + longest[0] + (kind == BC_ENRICH_DOUBLE ? longest[1] : 0u);
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
+  const int k = kind == BC_ENRICH_SINGLE ? 0 : 1;
+  if ((rc = ensure_raw_enrich(e, k, proj)) != BC_OK) return rc;
+  if (e->re_n[k] == 0) return BC_OK;
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
+  v.n = e->re_n[k];
+  v.n_seg = e->re_segs[k];
+  v.keys = (const uint64_t*)e->d_re[k];
+  v.sums = v.keys + v.n;
+  v.seg_start = v.sums + v.n;
+  v.cols = d_cols;
+  v.label_off = e->d_label_off;
+  v.label_bytes = e->d_label_bytes;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
+extern "C" {
+
+int bc_engine_render_raw_enriched(bc_engine* e, int kind, uint32_t sample_idx, bc_text_fn fn, void* user, uint64_t* n_rows) {
+  return render_raw_enriched(e, "bc_engine_render_raw_enriched", false, kind, &sample_idx, 1, fn, user, n_rows);
+}
+
+int bc_engine_render_raw_enriched_merged(bc_engine* e, int kind, const uint32_t* sample_idx, uint32_t n_samples, bc_text_fn fn,
+                                         void* user, uint64_t* n_rows) {
+  return render_raw_enriched(e, "bc_engine_render_raw_enriched_merged", true, kind, sample_idx, n_samples, fn, user, n_rows);
+}
+
+int bc_engine_raw_enrich_reduces(const bc_engine* e, uint64_t* n) {
+  *n = e->raw_enrich_builds;
+  return BC_OK;
+}
+
+int bc_engine_raw_enrich_reduce_ms(const bc_engine* e, double* ms) {
+  *ms = (double)e->raw_enrich_ms;
   return BC_OK;
 }
 
