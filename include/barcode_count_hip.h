@@ -451,6 +451,13 @@ const char *bc_engine_kernel_name(bc_engine *e);
  * plans with a bit map, BC_COUNT_LOG); 0 when every submit counted with per-read atomics.  One fold per chunk of at
  * most BC_COUNT_LOG_CHUNK reads of a log-mode submit.  Read-only: does not wait for the device. */
 int bc_engine_count_log_folds(const bc_engine *e, uint64_t *n);
+/* Reads submitted to the lane-per-read kernel under a wide-key plan since the engine was created.  A wide-key plan (a
+ * raw capture or a random barcode above 27 bases, or captures that overflow the 64-bit key together) runs on that
+ * kernel when BC_WIDE_LANE=1 was set at bc_engine_create and the plan is within the kernel's widths (groups, known
+ * barcodes and random barcode of at most 32 bases, a format of at most 320, at most 31 constant errors); batches
+ * above 320 bases go to the wave-per-read kernel as ever and are not counted here.  0 with the switch off (the
+ * default) or an ineligible plan.  The counts are the same either way.  Read-only: does not wait for the device. */
+int bc_engine_wide_lane_reads(const bc_engine *e, uint64_t *n);
 /* Shader clock right now (MHz), measured by a 0.3 ms probe kernel on the engine's stream against the
  * 100 MHz reference counter.  Call it straight after the work of interest: the clock sags under power
  * and thermal limits, and the match kernel's time follows it. */

@@ -240,6 +240,13 @@ class Engine:
         _check(self._lib, self._lib.bc_engine_count_log_folds(self._e, C.byref(n)))
         return n.value
 
+    def wide_lane_reads(self):
+        """reads submitted to the lane-per-read kernel under a wide-key plan since the engine was created (BC_WIDE_LANE=1
+        and an eligible plan; 0 otherwise: such reads then went to the wave-per-read kernel)"""
+        n = C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_wide_lane_reads(self._e, C.byref(n)))
+        return n.value
+
     def enrich_render_passes(self):
         """table passes made for the sums behind render_enriched() / render_enriched_merged() since the engine was created"""
         n = C.c_uint64()

@@ -122,6 +122,7 @@ ENGINE_API = {
     "bc_table_sum_u8": (_int, [_vp, _u32, _u64, _vp, _int, _vp]),
     "bc_engine_kernel_name": (_cp, [_vp]),
     "bc_engine_count_log_folds": (_int, [_vp, C.POINTER(C.c_uint64)]),
+    "bc_engine_wide_lane_reads": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_engine_enrich_render_passes": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_engine_sclk_mhz": (_int, [_vp, C.POINTER(C.c_double)]),
     "bc_plan_precompile": (_int, [_vp, _u32, _u32, _int, _cp]),  # lives with the engine: it drives the device compiler

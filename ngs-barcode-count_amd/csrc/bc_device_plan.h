@@ -37,6 +37,9 @@ constexpr uint16_t kFail16 = 0xFFFFu;
 constexpr uint32_t kLhashMul1 = 0x9E3779u;  // 24-bit multipliers: keys are below 2^20 (len <= 10), so the
 constexpr uint32_t kLhashMul2 = 0x85EBCBu;  // product fits the full-rate 24-bit multiply
 constexpr uint32_t kLhashMaxVec = 2048;  // 32 KiB of LDS per workgroup at most
+// wide keys (bc_long.h): fingerprint + payload words of a key at most, and what an empty slot's word 0 holds
+constexpr int kMaxKeyWords = 8;
+constexpr unsigned long long kWideEmpty = ~0ull;
 // bucket of a key: 16 well-mixed bits of key * mul, scaled to [0, nb) -- nb need not be a power of two,
 // which lets a table be sized to its load instead of the next power of two (LDS is what limits
 // how many wavefronts stay resident).  Three full-rate 24-bit multiplies / shifts.
@@ -119,7 +122,7 @@ struct DevGroup {
   // guides is 4 MiB and mostly stays in the XCD's L2) -- entry = r1 | r2 << len | index << 2 len, the bucket's
   // reference count (capped at 7) in the top three bits of its first entry.  0: sixteen-byte entries.
   uint32_t tier_compact;
-  uint32_t pad_;
+  uint32_t key_bit;         // wide keys (DevPlan::wide): first payload bit of this group's field, as in LongGroup (bc_long.h)
   // ... and a middle one between the coarse index and the full one (budgets of four mismatches and more): seed3_nb = 4
   // blocks catch every reference within three mismatches.  One capture in a thousand needs it, but the full index's
   // buckets (one reference in 256 each, a dozen dependent round trips for 100 k references) held its whole wavefront.
@@ -172,6 +175,13 @@ struct DevPlan {
   uint64_t lhash_a;
   uint32_t ablate;      // perf-debug only, honoured by -DBC_EXPERIMENT builds alone (`make experiment-lib`): bit mask of
                         // phases to skip; results are then wrong.  The release library ignores the field (abl() == 0).
+  // Wide keys on the lane-per-read kernel (bc_plan::lower with allow_wide): the captures do not fit the 64-bit tuple key
+  // and are counted under the key of the wave-per-read kernel (bc_long.h) -- word 0 a fingerprint, then per group 32 bits
+  // of reference index or the three bit planes of a raw capture, the random barcode's planes last.  Such a plan is
+  // sparse, its table strides and rspace are 0, and the kernel is the kWide instantiation (bc_kernel.h).
+  uint32_t wide;
+  uint32_t key_words;   // fingerprint + payload words (1 when not wide)
+  uint32_t rnd_bit;     // first payload bit of the random barcode's planes
   // Per position class a program that walks the class's format positions in ascending order,
   // shifting the class vector right by the distance to the next position (0..31 per shift).
   //   prog_mode 0: prog[0 .. n3) are full triples s1 | s2 << 8 | s3 << 16 (three positions each, a
@@ -194,7 +204,7 @@ struct DevPlan {
   // needs the search beyond one mismatch may wait in the wave's queue until four of them share one coarse-index probe
   // (bc_kernel.h).
   BC_HD bool defer_search() const {
-    return n_groups == 1u && !has_random && !sparse && groups[0].mode == kSetHash && groups[0].seed_nb != 0u &&
+    return n_groups == 1u && !has_random && !sparse && !wide && groups[0].mode == kSetHash && groups[0].seed_nb != 0u &&
            groups[0].seed2_nb != 0u && groups[0].seed2_nb <= 3u && groups[0].n_odd == 0u;
   }
 #ifdef BC_EXPERIMENT
@@ -203,6 +213,46 @@ struct DevPlan {
   BC_HD constexpr uint32_t abl() const { return 0u; }
 #endif
 };
+
+// ---- wide keys: what the two match kernels and the host share ------------------------------------------------------
+BC_HD uint64_t wide_mix(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+// word 0 of a key: a fingerprint of its payload words, top bit clear (so it never equals kWideEmpty).  (Unrolled with
+// a guard so that a key held in registers is never indexed by a run-time value.)
+BC_HD uint64_t wide_fingerprint(const uint64_t* key, uint32_t W) {
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+  for (uint32_t w = 1; w < (uint32_t)kMaxKeyWords; ++w)
+    if (w < W) h = wide_mix(h ^ key[w]) + w;
+  return h >> 1;
+}
+// `n` (1..32) bits of `v` ORed into a key held in registers at payload bit `at` (payload bit 0 = bit 0 of word 1):
+// every word is visited with a compile-time index; with `at` a constant (the specialised kernel) all but one or two
+// of the steps fold away.  A field may straddle two words; no shift count reaches 64.
+BC_HD void wide_or_bits(uint64_t (&key)[kMaxKeyWords], uint32_t at, uint32_t v, uint32_t n) {
+  const uint32_t w0 = 1u + (at >> 6), sh = at & 63u;
+  const uint64_t x = (uint64_t)(v & lowmask(n));
+  const bool spill = sh + n > 64u;  // (then sh > 32)
+  const uint64_t lo = x << sh, hi = spill ? x >> ((64u - sh) & 63u) : 0ull;
+#pragma unroll
+  for (uint32_t w = 1; w < (uint32_t)kMaxKeyWords; ++w) {
+    if (w == w0) key[w] |= lo;
+    if (w == w0 + 1u) key[w] |= hi;
+  }
+}
+// the three planes of a raw capture of `len` bases (ASCII bit 1, ASCII bit 2, 'N'; an 'N' clears the other two, as
+// wide_put_capture does byte by byte) at payload bit `at`
+BC_HD void wide_or_planes(uint64_t (&key)[kMaxKeyWords], uint32_t at, uint32_t q1, uint32_t q2, uint32_t qn, uint32_t len) {
+  wide_or_bits(key, at, q1 & ~qn, len);
+  wide_or_bits(key, at + len, q2 & ~qn, len);
+  wide_or_bits(key, at + 2u * len, qn, len);
+}
 
 constexpr int kNCounters = 8;      // BC_NCOUNTERS
 constexpr int kTotalReads = 6;     // BC_TOTAL_READS

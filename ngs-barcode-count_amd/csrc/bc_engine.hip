@@ -48,6 +48,22 @@ __global__ __launch_bounds__(kTPB, ((NW <= 4 && NWW <= 2) ? BC_MIN_WAVES : 1)) v
                                      counters, trace_outcome, trace_idx, flags, count_log);
 }
 
+// ... for a plan with wide keys (DevPlan::wide): the key is assembled in registers and inserted by all lanes at once
+template <int NW, int NWW>
+__global__ __launch_bounds__(kTPB, ((NW <= 4 && NWW <= 2) ? BC_MIN_WAVES : 1)) void match_count_wide_kernel(
+    const DevPlan* __restrict__ plp, const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual,
+    const uint16_t* __restrict__ lens, const uint16_t* __restrict__ qlens, uint32_t stride, uint32_t read_len, uint32_t nd,
+    uint64_t n_reads, uint32_t region, unsigned long long* __restrict__ slots, uint32_t* __restrict__ vals,
+    uint32_t* __restrict__ ready, uint64_t smask, unsigned long long* __restrict__ counters,
+    uint8_t* __restrict__ trace_outcome, uint64_t* __restrict__ trace_idx, uint32_t flags) {
+  if (lens)
+    match_count_body<NW, NWW, true, false, true>(*plp, seq, qual, lens, qlens, stride, read_len, nd, n_reads, region, nullptr, nullptr,
+                                                 slots, vals, smask, counters, trace_outcome, trace_idx, flags, nullptr, ready);
+  else
+    match_count_body<NW, NWW, false, false, true>(*plp, seq, qual, lens, nullptr, stride, read_len, nd, n_reads, region, nullptr,
+                                                  nullptr, slots, vals, smask, counters, trace_outcome, trace_idx, flags, nullptr, ready);
+}
+
 // The wave-per-read kernel (bc_long.h): reads, groups, references and budgets beyond the lane-per-read kernel's widths
 __global__ __launch_bounds__(256) void long_match_kernel(const LongPlan* __restrict__ plp, const uint8_t* __restrict__ seq,
                                                          const uint8_t* __restrict__ qual, const uint16_t* __restrict__ lens,
@@ -579,7 +595,23 @@ static void engine_free(bc_engine* e) {
 
 static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_stream, void* table_mem) {
   e->src_plan = p;
-  if (!p->lower(e->h)) {
+  // BC_WIDE_LANE=1: a plan with wide keys whose groups, budgets and format are within the lane kernel's widths is
+  // lowered for that kernel (bc_plan::lower, allow_wide); default 0: such a plan runs on the wave-per-read kernel
+  const char* wl_env = getenv("BC_WIDE_LANE");
+  const bool allow_wide = wl_env && atoi(wl_env) != 0;
+  if (p->lower(e->h, allow_wide)) {
+    if (e->h.plan.wide) {
+      // the key layout of rows, renderers and exchange is read from the wave-per-read plan: lowered now (host side),
+      // uploaded when a batch above 320 bases needs that kernel (ensure_long)
+      if (!p->lower_long(e->lh)) return BC_ERR_UNSUPPORTED;
+      if (!e->lh.plan.wide || e->lh.plan.key_words != e->h.plan.key_words || e->lh.plan.rnd_bit != e->h.plan.rnd_bit) {
+        set_error("bc_engine_create: the two kernels' key layouts differ");  // (cannot happen: one helper lays out both)
+        return BC_ERR_STATE;
+      }
+      e->long_lowered = true;
+      e->key_words = e->h.plan.key_words;
+    }
+  } else {
     // not a plan for the lane-per-read kernel (a group or a known barcode above 32 bases, more than 31 constant errors
     // allowed, a format above 320 bases): the wave-per-read kernel takes every batch
     const std::string why = get_error();
@@ -588,6 +620,7 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
       return BC_ERR_UNSUPPORTED;
     }
     e->long_only = true;
+    e->long_lowered = true;
     // the fields of the lane plan that results, keys and rows are read from
     DevPlan& P = e->h.plan;
     memset(&P, 0, sizeof(P));
@@ -935,12 +968,13 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     set_error("read stride too large for one LDS tile");
     return BC_ERR_UNSUPPORTED;
   }
-  auto kern = match_count_kernel<NW, NWW>;
-  if (s.lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+  const bool wide = e->h.plan.wide != 0;  // (a sparse plan: no bit map, no log, no hot-counter cache)
+  const void* kern = wide ? (const void*)match_count_wide_kernel<NW, NWW> : (const void*)match_count_kernel<NW, NWW>;
+  if (s.lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
   // persistent grid: as many workgroups as the chip holds at once (or fewer for a small batch), at the LDS this launch
   // asks for
   int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kTPB, lds));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kTPB, lds));
   if (per_cu < 1) per_cu = 1;
   const uint64_t resident = (uint64_t)per_cu * e->n_cus;
   const uint64_t blocks = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, resident);
@@ -996,14 +1030,20 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
       uint64_t a_smask = e->n_slots ? e->n_slots - 1 : 0;
       uint32_t a_flags = (s.pipe ? 1u : 0u) | (s.tables_jit ? 2u : 0u) | (s.hot_jit && hot_on ? 4u : 0u);
       void* args[] = {&a_seq, &a_qual, &a_lens, &a_qlens, &stride, &read_len, &nd, &a_n, &a_region, &e->d_table, &e->d_bits, &e->d_slots,
-                      &e->d_vals, &a_smask, &e->d_counters, &a_to, &a_ti, &a_flags, &a_log};
+                      &e->d_vals, &a_smask, &e->d_counters, &a_to, &a_ti, &a_flags, &a_log,
+                      &e->d_ready};  // (the last one: the kernel of a wide-key plan only, bc_jit.hip jit_source)
       const uint64_t grid = std::min<uint64_t>(blocks_jit, (n_c + kTPB - 1) / kTPB);
       HIP_TRY(hipModuleLaunchKernel(jit_fn, (uint32_t)grid, 1, 1, kTPB, 1, 1, lds_jit, e->stream, args, nullptr));
     } else {
       const uint64_t grid = std::min<uint64_t>(blocks, (n_c + kTPB - 1) / kTPB);
-      hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual, a_lens, a_qlens, stride, read_len,
-                         nd, a_n, s.region, e->d_table, e->d_bits, e->d_slots, e->d_vals, e->n_slots ? e->n_slots - 1 : 0, e->d_counters,
-                         a_to, a_ti, flags, a_log);
+      if (wide)
+        hipLaunchKernelGGL((match_count_wide_kernel<NW, NWW>), dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual,
+                           a_lens, a_qlens, stride, read_len, nd, a_n, s.region, e->d_slots, e->d_vals, e->d_ready,
+                           e->n_slots ? e->n_slots - 1 : 0, e->d_counters, a_to, a_ti, flags);
+      else
+        hipLaunchKernelGGL((match_count_kernel<NW, NWW>), dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual, a_lens,
+                           a_qlens, stride, read_len, nd, a_n, s.region, e->d_table, e->d_bits, e->d_slots, e->d_vals,
+                           e->n_slots ? e->n_slots - 1 : 0, e->d_counters, a_to, a_ti, flags, a_log);
     }
     HIP_TRY(hipGetLastError());
     if (use_log) {
@@ -1023,6 +1063,7 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   }
   e->last_kernel = std::string(jit_fn ? "bc_jit_match_count<" : "match_count_kernel<") +
                    std::to_string(jit_fn ? s.jit.NW : NW) + "," + std::to_string(jit_fn ? s.jit.NWW : NWW) + ">";
+  if (wide) e->wide_lane_reads += n_reads;
   e->last_key = jit_fn ? s.key : 0;
   e->last_lds = jit_fn ? lds_jit : lds;
   e->last_grid = (uint32_t)std::min<uint64_t>(jit_fn ? blocks_jit : blocks, (std::min<uint64_t>(chunk, n_reads) + kTPB - 1) / kTPB);
@@ -1037,7 +1078,8 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
 // the wave-per-read plan on the device (once per engine)
 static int ensure_long(bc_engine* e) {
   if (e->long_ready) return BC_OK;
-  if (!e->long_only && !e->src_plan->lower_long(e->lh)) return BC_ERR_UNSUPPORTED;
+  if (!e->long_lowered && !e->src_plan->lower_long(e->lh)) return BC_ERR_UNSUPPORTED;
+  e->long_lowered = true;
   LongPlan& Q = e->lh.plan;
   int rc;
   if ((rc = upload(e, e->lh.const_pos.data(), e->lh.const_pos.size() * 4, &Q.const_pos_a))) return rc;
@@ -2259,6 +2301,11 @@ int bc_internal_last_launch(const bc_engine* e, uint64_t* key, uint32_t* lds_byt
 
 int bc_engine_count_log_folds(const bc_engine* e, uint64_t* n) {
   *n = e->log_folds;
+  return BC_OK;
+}
+
+int bc_engine_wide_lane_reads(const bc_engine* e, uint64_t* n) {
+  *n = e->wide_lane_reads;
   return BC_OK;
 }
 

@@ -151,6 +151,10 @@ struct bc_engine {
   // the wave-per-read kernel's plan (bc_long.h): built when a submit needs it -- reads above 320 bases -- or at
   // creation when the lane-per-read kernel cannot run the plan at all (long_only)
   bool long_only = false, long_ready = false;
+  bool long_lowered = false;          // lh holds the lowered plan already (long_only, or a wide-key lane plan: the key
+                                      // layout that rows, renderers and exchange read is lh's)
+  uint64_t wide_lane_reads = 0;       // reads submitted to the lane-per-read kernel under a wide-key plan (h.plan.wide:
+                                      // BC_WIDE_LANE=1 and an eligible plan) since creation (bc_engine_wide_lane_reads)
   bc::LongHost lh;
   bc::LongPlan* d_long = nullptr;
   const bc_plan* src_plan = nullptr;  // (the caller keeps the plan alive for the engine's lifetime)

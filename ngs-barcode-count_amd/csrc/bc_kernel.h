@@ -4,6 +4,7 @@
 // compile-time constant, so every shift, offset and loop bound of the scheme becomes an immediate).
 #pragma once
 #include "bc_lane.h"
+#include "bc_long.h"  // wide keys: wide_insert_lanes
 
 #ifdef BC_PROFILE
 // wall-clock breakdown of a wave's tile loop: clock ticks between consecutive marks, summed over all waves
@@ -830,7 +831,9 @@ struct DeviceOps {
 // kLens: per-read lengths are given.  A separate instantiation because the length load would
 // otherwise put a full vector-memory wait into every iteration, fetches in flight or not.
 // kAligned: the stride is a multiple of 4 (known only to a kernel specialised for its batch shape)
-template <int NW, int NWW, bool kLens, bool kAligned = false>
+// kWide: the plan counts under wide keys (DevPlan::wide; `ready`: the table's published flags).  A template argument
+// so that no other instantiation carries the key's registers or a branch for them.
+template <int NW, int NWW, bool kLens, bool kAligned = false, bool kWide = false>
 __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_t* __restrict__ seq,
                                                  const uint8_t* __restrict__ qual, const uint16_t* __restrict__ lens,
                                                  const uint16_t* __restrict__ qlens,
@@ -839,7 +842,8 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
                                                  unsigned long long* __restrict__ slots, uint32_t* __restrict__ vals,
                                                  uint64_t smask, unsigned long long* __restrict__ counters,
                                                  uint8_t* __restrict__ trace_outcome, uint64_t* __restrict__ trace_idx,
-                                                 uint32_t flags, uint32_t* __restrict__ count_log = nullptr) {
+                                                 uint32_t flags, uint32_t* __restrict__ count_log = nullptr,
+                                                 uint32_t* __restrict__ ready = nullptr) {
   extern __shared__ uint4 smem[];
   __shared__ uint32_t s_cnt[kNCounters];
   const uint32_t tid = threadIdx.x;
@@ -1017,15 +1021,27 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     uint32_t qlen = len;
     if (kLens && qlens && active) qlen = (uint32_t)qlens[wfirst + lane];
     const uint32_t base = (active ? lane : 0u) * stride;
-    const ReadResult r =
-        process_read<DeviceOps, NW, NWW, kAligned>(pl, ops, reinterpret_cast<const uint32_t*>(ops.tile), base, len, qlen, nd, active);
+    const ReadResultT<kWide> r = process_read<DeviceOps, NW, NWW, kAligned, kWide>(
+        pl, ops, reinterpret_cast<const uint32_t*>(ops.tile), base, len, qlen, nd, active);
 
     ops.mark(8);
     uint32_t outcome = r.outcome;
     // (outcome kPending: the read's one barcode needs the seed indexes -- ops.nearest.  It is queued at the end of this
     // iteration and judged and counted there, or at the end of a later one when four are together, at the latest with
     // the wave's last tile.  Until then the read is in no outcome counter; it is in TotalReads below.)
-    if (pl.has_random) {
+    uint64_t wide_slot = 0;
+    if constexpr (kWide) {
+      // Results::add_count under a wide key (info.rs:742-802), as the wave-per-read kernel does it: a set of (tuple,
+      // random) keys -- a key already present makes the read a duplicate -- or a map of tuple counts (added to below).
+      // All lanes insert together (bc_long.h wide_insert_lanes: why that cannot hang); the compare-and-swaps and the
+      // loads of the insert are waited for inside it.
+      const bool ins = active && outcome == kMatched && (pl.has_random || !pl.discard_counts);
+      if (__any(ins)) {
+        bool is_new;
+        wide_slot = wide_insert_lanes(slots, ready, smask, pl.key_words, r.wkey, ins, is_new);
+        if (pl.has_random && ins && !is_new) outcome = kDuplicate;
+      }
+    } else if (pl.has_random) {
       // Results::add_count with a random barcode (info.rs:770-802): insert (tuple, random) into the
       // set; an element already present makes the read a duplicate (parse.rs:65-69)
       if (active && outcome == kMatched && !set_insert(slots, smask, r.dense_idx * pl.rspace + r.rcode))
@@ -1040,7 +1056,10 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     acc_cnt[kTotalReads] += n_w;
     if (trace_outcome && active && !(queues && outcome == kPending)) {
       trace_outcome[wfirst + lane] = (uint8_t)outcome;
-      trace_idx[wfirst + lane] = pl.has_random ? r.dense_idx * pl.rspace + r.rcode : r.dense_idx;
+      if constexpr (kWide)  // word 0 of the key for a matched or duplicate read, as long_match_kernel writes it
+        trace_idx[wfirst + lane] = (outcome == kMatched || outcome == kDuplicate) ? r.wkey[0] : 0ull;
+      else
+        trace_idx[wfirst + lane] = pl.has_random ? r.dense_idx * pl.rspace + r.rcode : r.dense_idx;
     }
     // the previous tile's first-occurrence probes, before anything new is requested (what is still in flight now was
     // requested long ago): a bit that was set already makes the read a repeat, which goes to the table
@@ -1070,7 +1089,11 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
       if (direct_tiles) --direct_tiles;
     }
     first_on = 0u;
-    if (!pl.has_random) {
+    if constexpr (kWide) {
+      // the count of the key's slot: one no-return atomic, not waited for (pending_add stays 0: fewer operations
+      // allowed in flight at the next wait than there are is always safe)
+      if (!pl.has_random && active && outcome == kMatched && !pl.discard_counts) atomicAdd(&vals[wide_slot], 1u);
+    } else if (!pl.has_random) {
       bool add = active && outcome == kMatched && !pl.discard_counts && !(pl.abl() & 0x4u);
       if (hot && !pl.sparse && __any(add)) add = hot_count(add, (uint32_t)r.dense_idx);
       if (logm) {

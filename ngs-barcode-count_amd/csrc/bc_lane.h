@@ -1024,6 +1024,14 @@ struct ReadResult {
   uint64_t dense_idx;  // index into the dense (sample, tuple) counter table
   uint64_t rcode;      // base-5 code of the random barcode (0 without one)
 };
+// ... and, for a plan with wide keys (DevPlan::wide), the key of a read that ended kMatched: word 0 the fingerprint,
+// then the payload (bc_long.h), in registers.  dense_idx and rcode are 0 then.
+template <bool kWide>
+struct ReadResultT : ReadResult {};
+template <>
+struct ReadResultT<true> : ReadResult {
+  uint64_t wkey[kMaxKeyWords];
+};
 
 // Ops must provide:
 //   bool any(bool)                               -- wave vote
@@ -1050,14 +1058,20 @@ BC_HD void ops_quality_consumed(Ops&, long) {}  // an Ops without the hook
 
 // NW = 32-base words per read; NWW = words of candidate offsets / repair windows (len - L + 1 <= 32*NWW)
 // kAligned: base is a multiple of 4 for every lane (the stride is)
-template <class Ops, int NW, int NWW, bool kAligned = false>
+// kWide: the plan counts under wide keys (pl.wide): the key is assembled from the captures' planes and the verdicts'
+// indexes; compiled out of every other instantiation
+template <class Ops, int NW, int NWW, bool kAligned = false, bool kWide = false>
 // len / qlen: length of the sequence line / of the quality line (they differ in trimmed or damaged files)
-BC_HD ReadResult process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32, uint32_t base, uint32_t len,
-                              uint32_t qlen, uint32_t nd, bool active) {
-  ReadResult res;
+BC_HD ReadResultT<kWide> process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32, uint32_t base, uint32_t len,
+                                      uint32_t qlen, uint32_t nd, bool active) {
+  ReadResultT<kWide> res;
   res.outcome = kMatched;
   res.dense_idx = 0;
   res.rcode = 0;
+  if constexpr (kWide) {
+#pragma unroll
+    for (int w = 0; w < kMaxKeyWords; ++w) res.wkey[w] = 0;
+  }
 
   Planes<NW> P;
   uint32_t bad;
@@ -1391,13 +1405,18 @@ BC_HD ReadResult process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32
               outcome = kPending;
               didx = (uint64_t)q1[u] | ((uint64_t)q2[u] << 32);
               pending_n = qn[u];
-            } else
+            } else if constexpr (kWide)
+              wide_or_bits(res.wkey, G.key_bit, r[u], 32u);  // the reference's index, as wide_put(.., verdict, 32)
+            else
               didx += (uint64_t)r[u] * G.table_stride;
           }
         } else if (pre_ok && outcome == kMatched) {
           // no known set: the capture is taken as it is (parse.rs:453-454, 487)
           if (qx[u]) raw_foreign = true;  // a byte outside ACGTN has no code -- matters only if the read ends up counted
-          didx += base5_code(q1[u], q2[u], qn[u], G.len) * G.table_stride;
+          if constexpr (kWide)
+            wide_or_planes(res.wkey, G.key_bit, q1[u], q2[u], qn[u], G.len);
+          else
+            didx += base5_code(q1[u], q2[u], qn[u], G.len) * G.table_stride;
         }
       }
     }
@@ -1412,8 +1431,12 @@ BC_HD ReadResult process_read(const DevPlan& pl, Ops& ops, const uint32_t* seq32
     extract_planes<NW>(P, pl.rnd_off, pl.rnd_len, r1, r2, rn);
     const uint32_t rx = anyx ? extract_uniform<NW>(P.px, pl.rnd_off, pl.rnd_len) : 0u;
     if (rx && active && outcome == kMatched) unsupported = true;  // a byte outside ACGTN has no code
-    res.rcode = base5_code(r1, r2, rn, pl.rnd_len);
+    if constexpr (kWide)
+      wide_or_planes(res.wkey, pl.rnd_bit, r1, r2, rn, pl.rnd_len);
+    else
+      res.rcode = base5_code(r1, r2, rn, pl.rnd_len);
   }
+  if constexpr (kWide) res.wkey[0] = wide_fingerprint(res.wkey, pl.key_words);  // (used for kMatched reads only)
   if (unsupported) outcome = kUnsupported;
   if (pl.defer_search() && outcome == kPending) res.rcode = pending_n;
   res.outcome = outcome;

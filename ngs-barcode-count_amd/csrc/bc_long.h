@@ -19,8 +19,7 @@
 
 namespace bc {
 
-constexpr int kMaxKeyWords = 8;
-constexpr unsigned long long kWideEmpty = ~0ull;
+// (kMaxKeyWords, kWideEmpty, wide_mix and wide_fingerprint: bc_device_plan.h, shared with the lane-per-read kernel)
 
 struct LongGroup {
   uint32_t type;     // GroupType
@@ -48,7 +47,8 @@ struct LongPlan {
   LongGroup groups[kMaxGroups];
 };
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+#ifndef BC_JIT_TU  // (a scheme-specialised lane kernel takes the wide-key insert from this file and nothing else)
 __device__ __forceinline__ uint32_t long_wave_sum(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
@@ -62,22 +62,9 @@ __device__ __forceinline__ uint32_t long_wave_min(uint32_t v) {
   }
   return v;
 }
+#endif
 
 // ---- wide keys ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t wide_mix(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-// word 0 of a key: a fingerprint of its payload words, top bit clear (so it never equals kWideEmpty)
-__device__ __forceinline__ uint64_t wide_fingerprint(const uint64_t* key, uint32_t W) {
-  uint64_t h = 0x9E3779B97F4A7C15ull;
-  for (uint32_t w = 1; w < W; ++w) h = wide_mix(h ^ key[w]) + w;
-  return h >> 1;
-}
 // `n` (<= 32) bits of `v` into the payload at bit `at` (payload bit 0 = bit 0 of word 1)
 __device__ __forceinline__ void wide_put(uint64_t* key, uint32_t at, uint32_t v, uint32_t n) {
   const uint32_t w = 1u + (at >> 6), sh = at & 63u;
@@ -129,6 +116,77 @@ __device__ __forceinline__ uint64_t wide_find_or_insert(unsigned long long* __re
   }
 }
 
+// The same insert for ALL lanes of a wavefront at once (the lane-per-read kernel: a key per lane, held in registers),
+// over the same slots, ready flags and counts.  Every lane of the wavefront calls it; the lanes with `want` insert
+// their key and get its slot (is_new as above).
+//
+// Why this cannot hang where 64 lanes inside wide_find_or_insert would: that function WAITS inside an iteration (for
+// the ready flag of a slot that carries its fingerprint), and a lane waiting for an owner of its own wavefront keeps
+// that owner from ever reaching its publish.  Here nothing waits inside an iteration.  There is one loop, and in every
+// iteration
+//   (a) the lanes still probing try to claim their current slot (compare-and-swap on word 0);
+//   (b) every lane that claimed one stores its payload and release-stores the ready flag -- unconditionally, in the very
+//       iteration of its claim, with nothing between the claim and the publish that depends on another lane;
+//   (c) every lane that met its own fingerprint acquire-loads the ready flag ONCE: 0 -> it keeps the slot and goes
+//       round again (the claim is not repeated: word 0 of a claimed slot never changes while a kernel runs); 1 -> it
+//       compares the payload, and is done on equal (is_new = false) or moves on;
+//   (d) lanes that met another fingerprint move on.
+// The argument rests on one property: no lane waits for another INSIDE an iteration, so every iteration ends, and an
+// owner's publish (b) is in the iteration of its claim whatever the other lanes meet.  It does not rest on (b) coming
+// before (c): the two are exclusive per lane and may be laid out in either order.  A finder whose owner is in its own
+// wavefront sees the flag in (c) of the same iteration, or -- (c) first, or the store not yet visible -- finds it clear,
+// keeps the slot and sees it a round later, by when the owner's iteration, publish included, is over.  An owner in
+// another wavefront is between its claim and its publish for a bounded number of its own instructions, whatever this
+// wavefront does, so a lane going round in (c) sees the flag after boundedly many rounds.  Probing ends because set_reserve
+// keeps the table at most half full, counting every submitted read as a possible new key: a probe sequence meets an
+// empty slot.  Lanes of one wavefront with the same key: the hardware serialises their compare-and-swaps in (a), one
+// wins and publishes in (b), the others meet their fingerprint and find the flag set and the payload equal in (c), in
+// that round or the next -- one winner, n - 1 finds.
+__device__ __forceinline__ uint64_t wide_insert_lanes(unsigned long long* __restrict__ slots, uint32_t* __restrict__ ready,
+                                                      uint64_t mask, uint32_t W, const uint64_t (&key)[kMaxKeyWords], bool want,
+                                                      bool& is_new) {
+  uint64_t h = wide_mix(key[0]) & mask;
+  bool probing = want;   // no slot yet
+  bool holding = false;  // the current slot carries this lane's fingerprint, its payload is not published yet
+  is_new = false;
+  while (__any(probing)) {
+    unsigned long long* s = slots + h * W;
+    // (a)
+    unsigned long long old = (unsigned long long)key[0];
+    if (probing && !holding) old = atomicCAS(s, kWideEmpty, (unsigned long long)key[0]);
+    // (b)
+    if (probing && !holding && old == kWideEmpty) {
+#pragma unroll
+      for (uint32_t w = 1; w < (uint32_t)kMaxKeyWords; ++w)
+        if (w < W) __hip_atomic_store(s + w, (unsigned long long)key[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ready + h, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      is_new = true;
+      probing = false;
+    }
+    // (c)
+    bool advance = probing && old != (unsigned long long)key[0];  // (d)
+    if (probing && old == (unsigned long long)key[0]) {
+      if (__hip_atomic_load(ready + h, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+        holding = true;
+      } else {
+        bool same = true;
+#pragma unroll
+        for (uint32_t w = 1; w < (uint32_t)kMaxKeyWords; ++w)
+          if (w < W) same = same && __hip_atomic_load(s + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)key[w];
+        holding = false;
+        if (same)
+          probing = false;
+        else
+          advance = true;
+      }
+    }
+    if (advance) h = (h + 1) & mask;
+    if (__any(holding)) __builtin_amdgcn_s_sleep(1);
+  }
+  return h;
+}
+
+#ifndef BC_JIT_TU
 // one read by one wavefront; returns the Outcome and, for a read that passed every test, its table / key index and
 // the base-5 code of its random barcode -- or, for a plan with wide keys, the key in wide_key[0 .. key_words)
 // (wave-private memory, written by lane 0)
@@ -312,6 +370,7 @@ __device__ __forceinline__ uint32_t long_match_read(const LongPlan& pl, const ui
   dense_idx = didx;
   return kMatched;
 }
+#endif  // BC_JIT_TU
 #endif
 
 }  // namespace bc

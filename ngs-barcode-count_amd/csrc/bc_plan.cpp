@@ -138,7 +138,71 @@ static bool pack_ref(const std::string& s, uint32_t& r1, uint32_t& r2, uint32_t&
   return true;
 }
 
-bool bc_plan::lower(HostDevPlan& out) const {
+// Do the captures fit the one 64-bit mixed-radix key (index of a known set, base-5 code of a capture kept raw, base-5
+// code of the random barcode)?  If not -- a raw capture or a random barcode above 27 bases, or several that overflow
+// together -- the plan counts under wide keys (bc_long.h), whose payload is laid out here, group after group from bit 0:
+// 32 bits of reference index, or the capture's three bit planes; the random barcode's planes last.
+void bc_plan::wide_layout(WideLayout& out) const {
+  struct Field {
+    uint32_t len;
+    size_t n_refs;
+  };
+  std::vector<Field> order;
+  for (const auto& g : groups)
+    if (g.type == kGroupSample) order.push_back({g.len, samples.size()});
+  for (uint32_t b = 1; b <= barcode_num; ++b)
+    for (const auto& g : groups)
+      if (g.type == kGroupBarcode && g.number == b) order.push_back({g.len, counted[b - 1].size()});
+  bool wide = false;
+  // (the very tests lower() makes before it gives a plan with a 64-bit key to the lane-per-read kernel: both must agree
+  // on what such a key can hold, since an engine may run the two kernels side by side -- reads above 320 bases)
+  unsigned __int128 space = 1;
+  const unsigned __int128 limit = (unsigned __int128)1 << 63;
+  for (const Field& f : order) {
+    if (f.n_refs == 0) {
+      if (f.len > 27) wide = true;
+      for (uint32_t k = 0; k < f.len && space < limit; ++k) space *= 5;
+    } else {
+      space *= f.n_refs;
+    }
+    if (space >= limit) wide = true;
+  }
+  if (random_barcode && !wide)
+    for (const auto& g : groups) {
+      if (g.type != kGroupRandom) continue;
+      if (g.len > 27) {
+        wide = true;
+        continue;
+      }
+      unsigned __int128 rs = 1;
+      for (uint32_t k = 0; k < g.len; ++k) rs *= 5;
+      if (rs * space >= ((unsigned __int128)1 << 64) - 1) wide = true;
+    }
+  out = WideLayout();
+  out.wide = wide;
+  out.key_bit.assign(order.size(), 0);
+  if (!wide) return;
+  uint32_t bits = 0;
+  for (size_t i = 0; i < order.size(); ++i) {
+    out.key_bit[i] = bits;
+    bits += order[i].n_refs ? 32u : 3u * order[i].len;
+  }
+  if (random_barcode)
+    for (const auto& g : groups) {
+      if (g.type != kGroupRandom) continue;
+      out.rnd_bit = bits;
+      bits += 3u * g.len;
+    }
+  out.key_bits = bits;
+  out.key_words = 1u + (bits + 63u) / 64u;
+}
+
+static std::string wide_too_long(uint32_t key_bits) {
+  return "unsupported plan: the captures kept raw (no conversion file) and the random barcode take " + std::to_string(key_bits) +
+         " key bits; the engine's widest key holds " + std::to_string(64 * (kMaxKeyWords - 1));
+}
+
+bool bc_plan::lower(HostDevPlan& out, bool allow_wide) const {
   if (!unsupported.empty()) {
     set_error("unsupported scheme: " + unsupported);
     return false;
@@ -157,6 +221,17 @@ bool bc_plan::lower(HostDevPlan& out) const {
   }
   DevPlan& P = out.plan;
   memset(&P, 0, sizeof(P));
+  // wide keys on this kernel, when the caller takes them (else the width tests below refuse the plan as ever)
+  WideLayout wl;
+  if (allow_wide) wide_layout(wl);
+  const bool wide = allow_wide && wl.wide;
+  if (wide && wl.key_words > (uint32_t)kMaxKeyWords) {
+    set_error(wide_too_long(wl.key_bits));
+    return false;
+  }
+  P.wide = wide ? 1u : 0u;
+  P.key_words = wide ? wl.key_words : 1u;
+  P.rnd_bit = wide ? wl.rnd_bit : 0u;
   P.L = regex_length;  // bytes a match spans (shorter than format_string only for a token mixing 'N' and 'n')
   P.RL = (uint32_t)regions_string.size();
   P.max_const = max_constant;
@@ -278,7 +353,13 @@ bool bc_plan::lower(HostDevPlan& out) const {
     }
     G.n_refs = (uint32_t)pd.set->size();
     G.max_err = pd.max_err;
-    G.table_stride = (uint64_t)entries;
+    G.table_stride = wide ? 0 : (uint64_t)entries;
+    G.key_bit = wide ? wl.key_bit[i] : 0u;
+    if (G.n_refs == 0 && wide) {
+      G.mode = kSetNone;  // the capture's planes go into the key as they are
+      P.sparse = 1;
+      continue;
+    }
     if (G.n_refs == 0) {
       // no known set (sample_seqs.is_empty() parse.rs:453 / counted_barcode_seqs.is_empty() parse.rs:487):
       // the capture itself is the key; its base-5 code takes the place of a reference index
@@ -295,7 +376,7 @@ bool bc_plan::lower(HostDevPlan& out) const {
       }
       continue;
     }
-    entries *= G.n_refs;
+    if (!wide) entries *= G.n_refs;
     if (entries >= ((unsigned __int128)1 << 63)) {
       set_error("unsupported plan: the (sample, barcode tuple) space does not fit a 64-bit key");
       return false;
@@ -521,10 +602,22 @@ bool bc_plan::lower(HostDevPlan& out) const {
     set_error("unsupported plan: dense counter table above 2^40 entries");
     return false;
   }
-  out.table_entries = (uint64_t)entries;  // dense plans: table size; sparse plans: size of the tuple-key space
+  if (wide) P.sparse = 1;  // counts live in a key map (rows are read as text, bc_engine_row_text), whatever the sets are
+  out.table_entries = wide ? 0 : (uint64_t)entries;  // dense plans: table size; sparse plans: size of the tuple-key space
   if (random_barcode) {
     for (const auto& g : groups) {
       if (g.type != kGroupRandom) continue;
+      if (wide) {
+        if (g.len == 0 || g.len > 32) {
+          set_error("unsupported scheme: random barcodes under a wide key must be 1..32 bases on the lane-per-read kernel");
+          return false;
+        }
+        P.has_random = 1;
+        P.rnd_off = g.off;
+        P.rnd_len = g.len;
+        P.rspace = 0;
+        continue;
+      }
       if (g.len == 0 || g.len > 27) {
         set_error("unsupported scheme: random barcodes must be 1..27 bases");
         return false;
@@ -613,38 +706,11 @@ bool bc_plan::lower_long(LongHost& out) const {
   out.ref_off.assign(order.size(), {});
   out.n_samples = sample_barcode ? (uint32_t)samples.size() : 1u;
   P.discard_counts = (!sample_barcode && samples.size() > 0 && !random_barcode) ? 1u : 0u;
-  // Do the captures fit the one 64-bit mixed-radix key (index of a known set, base-5 code of a capture kept raw, base-5
-  // code of the random barcode)?  If not -- a raw capture or a random barcode above 27 bases, or several that overflow
-  // together -- the plan counts under wide keys (bc_long.h).
-  bool wide = false;
-  {
-    // (the very tests lower() makes before it gives a plan to the lane-per-read kernel: both must agree on what a
-    // 64-bit key can hold, since an engine may run the two kernels side by side -- reads above 320 bases)
-    unsigned __int128 space = 1;
-    const unsigned __int128 limit = (unsigned __int128)1 << 63;
-    for (const Pending& pd : order) {
-      if (pd.set->size() == 0) {
-        if (pd.g->len > 27) wide = true;
-        for (uint32_t k = 0; k < pd.g->len && space < limit; ++k) space *= 5;
-      } else {
-        space *= pd.set->size();
-      }
-      if (space >= limit) wide = true;
-    }
-    if (random_barcode && !wide)
-      for (const auto& g : groups) {
-        if (g.type != kGroupRandom) continue;
-        if (g.len > 27) {
-          wide = true;
-          continue;
-        }
-        unsigned __int128 rs = 1;
-        for (uint32_t k = 0; k < g.len; ++k) rs *= 5;
-        if (rs * space >= ((unsigned __int128)1 << 64) - 1) wide = true;
-      }
-  }
+  // one 64-bit mixed-radix key, or wide keys (bc_long.h)?  The layout is wide_layout()'s, shared with lower()
+  WideLayout wl;
+  wide_layout(wl);
+  const bool wide = wl.wide;
   unsigned __int128 entries = 1;
-  uint32_t key_bits = 0;
   for (int i = (int)order.size() - 1; i >= 0; --i) {
     const Pending& pd = order[i];
     LongGroup& G = P.groups[i];
@@ -678,12 +744,8 @@ bool bc_plan::lower_long(LongHost& out) const {
   P.key_words = 1;
   P.rnd_bit = 0;
   if (wide) {
-    // payload layout, group after group from bit 0: 32 bits of reference index, or the capture's three bit planes
     P.sparse = 1;  // counts live in a key map (rows are read as text, bc_engine_row_text), whatever the sets are
-    for (uint32_t i = 0; i < P.n_groups; ++i) {
-      P.groups[i].key_bit = key_bits;
-      key_bits += P.groups[i].n_refs ? 32u : 3u * P.groups[i].len;
-    }
+    for (uint32_t i = 0; i < P.n_groups; ++i) P.groups[i].key_bit = wl.key_bit[i];
   }
   out.table_entries = wide ? 0 : (uint64_t)entries;
   if (random_barcode) {
@@ -697,8 +759,7 @@ bool bc_plan::lower_long(LongHost& out) const {
       P.rnd_off = g.off;
       P.rnd_len = g.len;
       if (wide) {
-        P.rnd_bit = key_bits;
-        key_bits += 3u * g.len;
+        P.rnd_bit = wl.rnd_bit;
         P.rspace = 0;
       } else {
         unsigned __int128 space = 1;
@@ -708,10 +769,9 @@ bool bc_plan::lower_long(LongHost& out) const {
     }
   }
   if (wide) {
-    P.key_words = 1u + (key_bits + 63u) / 64u;
+    P.key_words = wl.key_words;
     if (P.key_words > (uint32_t)kMaxKeyWords) {
-      set_error("unsupported plan: the captures kept raw (no conversion file) and the random barcode take " +
-                std::to_string(key_bits) + " key bits; the engine's widest key holds " + std::to_string(64 * (kMaxKeyWords - 1)));
+      set_error(wide_too_long(wl.key_bits));
       return false;
     }
   }

@@ -64,6 +64,17 @@ struct HostDevPlan {
   uint32_t n_samples = 1;
 };
 
+// Where a plan's captures sit in a wide key (bc_long.h) -- or that they fit the one 64-bit mixed-radix key (wide =
+// false).  The one place that decides it: both match kernels, the renderers, the exchange and bc_engine_row_text read
+// keys of this layout out of one table.
+struct WideLayout {
+  bool wide = false;
+  uint32_t key_words = 1;          // fingerprint + payload words
+  uint32_t key_bits = 0;           // payload bits in use
+  uint32_t rnd_bit = 0;            // first payload bit of the random barcode's planes
+  std::vector<uint32_t> key_bit;   // per group, in plan order (sample first, then the counted barcodes)
+};
+
 // host form of the wave-per-read kernel's plan (bc_long.h): device pointers still null
 struct LongHost {
   LongPlan plan;
@@ -106,8 +117,12 @@ struct bc_plan {
   float min_quality = 0.0f;
 
   void recompute_budgets();
-  // lowers to the device form; false + set_error() when the engine cannot run the plan
-  bool lower(bc::HostDevPlan& out) const;
+  // lowers to the device form; false + set_error() when the engine cannot run the plan.  allow_wide: a plan whose
+  // captures need a wide key (wide_layout) is lowered to a lane plan that assembles that key (DevPlan::wide) when
+  // everything else is within the lane kernel's widths; without it such a plan is refused, as it always was.
+  bool lower(bc::HostDevPlan& out, bool allow_wide = false) const;
+  // groups in plan order, and where their fields sit in a wide key
+  void wide_layout(bc::WideLayout& out) const;
   // the same for the wave-per-read kernel: any read length, group length, reference length and constant budget
   bool lower_long(bc::LongHost& out) const;
   uint32_t quality_threshold(uint32_t run_len) const;
