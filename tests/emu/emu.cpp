@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <thread>
 #include <vector>
 
 #include "../../ngs-barcode-count_amd/csrc/bc_lane.h"
@@ -79,7 +80,9 @@ void run(const EmuPlan& E, const uint8_t* seq, const uint8_t* qual, const uint16
 
 extern "C" {
 
-void* emu_plan_create(const bc_plan* p) {
+// tables: also fill the direct correction tables (4^len entries, each a scan of the set); a caller that only reads the
+// layout (emu_group_layout) does without them
+static void* plan_create(const bc_plan* p, bool tables) {
   EmuPlan* E = new EmuPlan();
   if (!p->lower(E->h)) {
     delete E;
@@ -101,21 +104,52 @@ void* emu_plan_create(const bc_plan* p) {
     G.tier_off_a = (uint64_t)(uintptr_t)H.tier_off.data();
     G.tier_list_a = (uint64_t)(uintptr_t)H.tier_list.data();
     G.tier_bkt_a = (uint64_t)(uintptr_t)H.tier_bkt.data();
-    if (G.mode == bc::kSetDirect) {
+    if (G.mode == bc::kSetDirect && tables) {
       const uint32_t nq = 1u << (2 * G.len);
       E->dtables[g].resize(nq);
-      for (uint32_t q = 0; q < nq; ++q) E->dtables[g][q] = bc::dtable_entry(G, q);
-      G.dtable_a = (uint64_t)(uintptr_t)E->dtables[g].data();
+      uint32_t* out = E->dtables[g].data();
+      const uint32_t nt = nq >= (1u << 16) ? 8u : 1u;  // (a large table is 4^10 scans of the set)
+      std::vector<std::thread> pool;
+      for (uint32_t t = 0; t < nt; ++t)
+        pool.emplace_back([&G, out, nq, nt, t] {
+          for (uint32_t q = (uint64_t)nq * t / nt; q < (uint64_t)nq * (t + 1) / nt; ++q) out[q] = bc::dtable_entry(G, q);
+        });
+      for (auto& th : pool) th.join();
+      G.dtable_a = (uint64_t)(uintptr_t)out;
     }
   }
   return E;
 }
+
+void* emu_plan_create(const bc_plan* p) { return plan_create(p, true); }
+void* emu_plan_lower(const bc_plan* p) { return plan_create(p, false); }
 
 void emu_plan_destroy(void* e) { delete (EmuPlan*)e; }
 
 uint64_t emu_table_entries(void* e) { return ((EmuPlan*)e)->h.table_entries; }
 int emu_discard_counts(void* e) { return (int)((EmuPlan*)e)->h.plan.discard_counts; }
 uint64_t emu_rspace(void* e) { return ((EmuPlan*)e)->h.plan.has_random ? ((EmuPlan*)e)->h.plan.rspace : 0; }
+
+// What lower() chose for group g, for tests that must know which search layer a set lands on: the scalars in the
+// order of emu_lib.LAYOUT_FIELDS, and the arrays of its indexes as lower() built them (emu_lib.LAYOUT_ARRAYS).
+int emu_group_layout(void* e, uint32_t g, uint32_t* fields, const uint32_t** arrays, uint64_t* sizes) {
+  const EmuPlan& E = *(EmuPlan*)e;
+  if (g >= E.h.plan.n_groups) return -1;
+  const bc::DevGroup& G = E.h.plan.groups[g];
+  const bc::HostSet& H = E.h.sets[g];
+  const uint32_t f[] = {G.mode,        G.seed_nb,     G.seed_blen,    G.seed2_nb, G.seed2_blen, G.seed3_nb,
+                        G.seed3_blen,  G.tier_blen,   G.tier_stride,  G.tier_compact, G.n_idx,  G.n_odd,
+                        G.lhash_nb,    G.lhash_complete, G.len,       G.n_refs,   G.max_err,
+                        (uint32_t)E.h.plan.defer_search()};
+  memcpy(fields, f, sizeof(f));
+  const std::vector<uint32_t>* a[] = {&H.seed_off, &H.seed_list, &H.seed2_off, &H.seed2_list, &H.seed3_off, &H.seed3_list,
+                                      &H.tier_off, &H.tier_list, &H.tier_bkt,  &H.odd_list,   &H.r1,        &H.r2};
+  for (size_t i = 0; i < sizeof(a) / sizeof(a[0]); ++i) {
+    arrays[i] = a[i]->data();
+    sizes[i] = a[i]->size();
+  }
+  return 0;
+}
 
 int emu_process2(void* e, const uint8_t* seq, const uint8_t* qual, const uint16_t* lens, const uint16_t* qlens, uint32_t stride,
                  uint32_t read_len, uint64_t n, uint8_t* outcomes, uint64_t* idx, uint64_t* rcode) {

@@ -23,18 +23,21 @@ def lib(variant="generic"):
         so, flags = VARIANTS[variant]
         if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
             subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared",
-                                   "-o", so] + flags + SRCS)
+                                   "-pthread", "-o", so] + flags + SRCS)
         import ngs_barcode_count_amd as pkg
         L = C.CDLL(so)
         pkg._lib.declare(L, pkg._lib.PLAN_API)
         L.emu_plan_create.restype = C.c_void_p
         L.emu_plan_create.argtypes = [C.c_void_p]
+        L.emu_plan_lower.restype = C.c_void_p
+        L.emu_plan_lower.argtypes = [C.c_void_p]
         L.emu_plan_destroy.argtypes = [C.c_void_p]
         L.emu_table_entries.restype = C.c_uint64
         L.emu_table_entries.argtypes = [C.c_void_p]
         L.emu_discard_counts.argtypes = [C.c_void_p]
         L.emu_process.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.emu_process2.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.emu_group_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.emu_rspace.restype = C.c_uint64
         L.emu_rspace.argtypes = [C.c_void_p]
         _libs[variant] = L
@@ -69,6 +72,34 @@ def open_plan(plan):
 
 def close_plan(plan, handle):
     plan._lib.emu_plan_destroy(handle)
+
+
+LAYOUT_FIELDS = ("mode", "seed_nb", "seed_blen", "seed2_nb", "seed2_blen", "seed3_nb", "seed3_blen", "tier_blen",
+                 "tier_stride", "tier_compact", "n_idx", "n_odd", "lhash_nb", "lhash_complete", "len", "n_refs", "max_err",
+                 "defer_search")
+LAYOUT_ARRAYS = ("seed_off", "seed_list", "seed2_off", "seed2_list", "seed3_off", "seed3_list", "tier_off", "tier_list",
+                 "tier_bkt", "odd_list", "r1", "r2")
+
+
+def group_layout(plan, group=0, handle=None):
+    """what bc_plan::lower chose for one group: {field: int} for LAYOUT_FIELDS (defer_search is the plan's) plus copies
+    of the index arrays of LAYOUT_ARRAYS (uint32; empty where the plan has no such index)"""
+    L = plan._lib
+    e = handle or L.emu_plan_lower(plan._p)
+    if not e:
+        raise RuntimeError(L.bc_last_error().decode())
+    fields = (C.c_uint32 * len(LAYOUT_FIELDS))()
+    ptrs = (C.POINTER(C.c_uint32) * len(LAYOUT_ARRAYS))()
+    sizes = (C.c_uint64 * len(LAYOUT_ARRAYS))()
+    rc = L.emu_group_layout(e, group, fields, ptrs, sizes)
+    out = dict(zip(LAYOUT_FIELDS, (int(v) for v in fields)))
+    if rc == 0:
+        for name, p, n in zip(LAYOUT_ARRAYS, ptrs, sizes):
+            out[name] = np.ctypeslib.as_array(p, shape=(int(n),)).copy() if n else np.zeros(0, dtype=np.uint32)
+    if not handle:
+        L.emu_plan_destroy(e)
+    assert rc == 0
+    return out
 
 
 def emulate(plan, seq, qual, lens, stride, read_len, with_random=False, qlens=None, handle=None):
