@@ -265,4 +265,30 @@ enum Outcome : uint32_t {
   kUnsupported = 7
 };
 
+// Outcome counters of a specialised match kernel (bc_kernel.h): every lane counts its own reads' outcomes in eight
+// 8-bit fields of one 64-bit value, field k for outcome k, and the wave adds the lanes up once every kPackTiles tiles
+// and with its last tile -- one shift and one add per tile instead of a vote, a bit count and an add per outcome.
+// A lane adds at most 1 per tile to one field, so 255 tiles cannot carry out of a field; the wave's sum is taken over
+// 16-bit halves (two fields per word, the fields between them masked out): 64 lanes x 255 = 16,320 < 2^16.
+constexpr uint32_t kPackTiles = 255u;
+BC_HD uint64_t outcome_pack(bool active, uint32_t outcome) { return (uint64_t)(active ? 1u : 0u) << (8u * outcome); }
+// the four words a wave sums: fields {0, 2}, {1, 3}, {4, 6}, {5, 7} in the low and high halves
+BC_HD void outcome_split(uint64_t pk, uint32_t (&w)[4]) {
+  const uint32_t lo = (uint32_t)pk, hi = (uint32_t)(pk >> 32);
+  w[0] = lo & 0x00FF00FFu;
+  w[1] = (lo >> 8) & 0x00FF00FFu;
+  w[2] = hi & 0x00FF00FFu;
+  w[3] = (hi >> 8) & 0x00FF00FFu;
+}
+// sums: the four words added up over the wave's lanes.  Field 6 (kPending, BC_TOTAL_READS' slot) is not an outcome.
+BC_HD void outcome_fold(const uint32_t (&sums)[4], uint32_t (&acc)[kNCounters]) {
+  acc[0] += sums[0] & 0xFFFFu;
+  acc[2] += sums[0] >> 16;
+  acc[1] += sums[1] & 0xFFFFu;
+  acc[3] += sums[1] >> 16;
+  acc[4] += sums[2] & 0xFFFFu;
+  acc[5] += sums[3] & 0xFFFFu;
+  acc[7] += sums[3] >> 16;
+}
+
 }  // namespace bc

@@ -732,7 +732,9 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
   if (const char* cm = getenv("BC_COUNT_LOG_MIN_READS")) e->log_min_reads = strtoull(cm, nullptr, 0);
   if (const char* cc = getenv("BC_COUNT_LOG_CHUNK")) {
     const uint64_t c = strtoull(cc, nullptr, 0) & ~63ull;
-    if (c) e->log_chunk = std::min<uint64_t>(c, 1ull << 27);
+    // (a log-mode specialised kernel numbers its tiles in 32 bits: bc_kernel.h tile_t)
+    static_assert(kLogChunkMax <= (1ull << 37), "tile_t: tile number + waves of the grid must not wrap");
+    if (c) e->log_chunk = std::min<uint64_t>(c, kLogChunkMax);
   }
   if (P.lhash_vec) {
     const int rc = upload(e, e->h.lhash.data(), e->h.lhash.size() * 4, &P.lhash_a);
@@ -987,9 +989,10 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   }
   hipFunction_t jit_fn = nullptr;
   e->reads_seen += n_reads;
+  // (a log-mode specialised kernel numbers its tiles in 32 bits, bc_kernel.h tile_t: log_chunk is 2^27 reads at most)
   if (NW <= 8 && NWW <= 4 && e->jit_mode != 0) {  // reads up to 256 bases; longer ones stay on the generic kernel
     int per_cu_jit = 1;
-    jit_fn = e->jit.function(e->h.plan, e->device, e->jit_mode, e->reads_seen, s, hot_on, &per_cu_jit);
+    jit_fn = e->jit.function(e->h.plan, e->device, e->jit_mode, e->reads_seen, s, jit_variant(s, use_log, hot_on), &per_cu_jit);
     resident_jit = (uint64_t)per_cu_jit * e->n_cus;
     if (jit_fn) blocks_jit = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, resident_jit);
   }

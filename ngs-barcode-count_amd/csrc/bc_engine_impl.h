@@ -59,6 +59,9 @@ struct ScratchGuard {
   }
 };
 
+// most reads of one log-mode match launch + fold (BC_COUNT_LOG_CHUNK is clamped to it)
+constexpr uint64_t kLogChunkMax = 1ull << 27;
+
 struct bc_engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -82,7 +85,7 @@ struct bc_engine {
   // at least log_min_reads reads (BC_COUNT_LOG_MIN_READS).  Either way the counts are the same.
   int count_log = 2;
   uint64_t log_min_reads = 1ull << 24;
-  uint64_t log_chunk = 1ull << 27;   // reads per match launch + fold (BC_COUNT_LOG_CHUNK, a multiple of 64)
+  uint64_t log_chunk = kLogChunkMax;   // reads per match launch + fold (BC_COUNT_LOG_CHUNK, a multiple of 64)
   bool log_hot = false;              // the hot-counter cache in log mode too (BC_COUNT_LOG_HOT=0|1; off: 4.62 vs 4.75 ms
                                      // for config 3's match kernel -- the fold's LDS atomics take hot tuples in stride)
   uint64_t log_cap = 0;              // entries allocated in d_log / d_grouped

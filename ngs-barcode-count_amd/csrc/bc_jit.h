@@ -38,6 +38,19 @@ struct JitShape {
   int min_waves = 3;          // waves per SIMD the register allocation must leave room for (__launch_bounds__)
 };
 
+// What a launch fixes beneath the shape key: how its reads are counted and whether the workgroups keep a hot-counter
+// cache.  A log-mode launch gets a kernel compiled for its variant (JIT_COUNT=1, JIT_HOT: bc_kernel.h), which carries
+// no counting atomic, bit-map probe or, with the cache off, cache.  A launch of the atomic path gets the source as it
+// always was, count and cache as launch arguments: one object for both its variants (jit_defines).  The variant is
+// part of the code object's cache name, not of MatchShape::key.
+struct JitVariant {
+  int count;  // 1: through the count log; 2: counting atomics
+  bool hot;   // hot-counter cache
+  uint32_t id() const { return count == 1 ? (hot ? 3u : 2u) : 0u;  }  // (the engine's map: one entry per code object)
+};
+// the variant of a launch: use_log / hot_on as launch_match decides them
+inline JitVariant jit_variant(const struct MatchShape& s, bool use_log, bool hot_on);
+
 // What a match launch derives from the plan and the batch shape, for the generic kernel and the specialised one
 struct MatchShape {
   int generic_nw;                   // the generic instantiation's NW
@@ -58,8 +71,11 @@ MatchShape match_shape(const DevPlan& P, uint64_t table_entries, uint32_t stride
                        uint32_t lds_limit, bool pipe, bool qshare, int lhash_mode);
 // BC_QUAL_REGION=own|shared (default shared): what engines and the ahead-of-time build pass as qshare
 bool qual_region_shared();
+inline JitVariant jit_variant(const MatchShape& s, bool use_log, bool hot_on) {
+  return JitVariant{use_log ? 1 : 2, s.hot_jit && hot_on};
+}
 
-// scheme-specialised kernels of one engine, one per MatchShape::key; destruction joins the workers and unloads the
+// scheme-specialised kernels of one engine, one per MatchShape::key and variant; destruction joins the workers and unloads the
 // modules
 struct JitKernels {
   struct Jit {
@@ -72,16 +88,16 @@ struct JitKernels {
     hipFunction_t fn = nullptr;
     int per_cu = 0, per_cu_cold = 0;  // workgroups per CU at lds_jit / lds_jit_cold
   };
-  std::map<uint64_t, std::unique_ptr<Jit>> slots;
+  std::map<std::pair<uint64_t, uint32_t>, std::unique_ptr<Jit>> slots;  // (shape key, JitVariant::id)
 
   JitKernels() = default;
   JitKernels(const JitKernels&) = delete;
   JitKernels& operator=(const JitKernels&) = delete;
   ~JitKernels();
   // The specialised kernel of one shape, if it can be had now (mode: BC_JIT as bc_engine::jit_mode reads it;
-  // reads_seen: reads submitted so far; hot_on: the launch uses the hot-counter cache, *per_cu: the workgroups a CU
-  // holds of such a launch).  Returns nullptr while the generic kernel must do.
-  hipFunction_t function(const DevPlan& plan, int device, int mode, uint64_t reads_seen, const MatchShape& s, bool hot_on,
+  // reads_seen: reads submitted so far; v: the launch's variant, *per_cu: the workgroups a CU holds of such a launch).
+  // Returns nullptr while the generic kernel must do.
+  hipFunction_t function(const DevPlan& plan, int device, int mode, uint64_t reads_seen, const MatchShape& s, const JitVariant& v,
                          int* per_cu);
 };
 

@@ -17,6 +17,31 @@ namespace bc {
 #define BC_TPB 256
 #endif
 constexpr int kTPB = BC_TPB;       // reads (lanes) per workgroup
+// What a launch of the generic kernel is told through its arguments and a specialised kernel has compiled in -- the
+// variants beneath a shape key (bc_jit.hip JitVariant); what a variant does not use is not in its code object.
+#ifndef JIT_COUNT
+#define JIT_COUNT 0  // 1: counts go through the log; 0: as `count_log` says (the generic kernel, the atomic path)
+#endif
+#ifndef JIT_HOT
+#define JIT_HOT (-1)  // the workgroup's hot-counter cache, 0 off / 1 on; -1: as flags bit 2 says
+#endif
+// The tile loop of a specialised LOG-MODE kernel (32-bit tile numbers, wave-uniform tile number, loop split by tile
+// kind, packed outcome counters: match_count_body).  A specialised kernel of the atomic path keeps the generic
+// kernel's loop, as it always had: its workloads were not measured with the new one.
+#if defined(BC_JIT_TU) && JIT_COUNT == 1
+#define BC_LOG_LOOP 1
+#endif
+#ifdef BC_LOG_LOOP
+// Tiles are numbered in 32 bits: a log-mode launch has 2^27 reads at most (bc_engine.hip log_chunk), so neither a
+// tile number nor a tile number plus the grid's waves wraps.
+typedef uint32_t tile_t;
+#else
+typedef uint64_t tile_t;
+#endif
+template <int K>
+struct TileKind {  // (match_count_body: which kind of tile an instance of the loop body is compiled for)
+  static constexpr int value = K;
+};
 #ifndef BC_MIN_WAVES
 #define BC_MIN_WAVES 3  // occupancy floor (waves per SIMD) the register allocator must honour
 #endif
@@ -853,7 +878,14 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   // vector registers; 98 and a spill without).  Elsewhere the scalar registers are the scarcer ones: config 2 ran 5 %
   // slower with it.
   const bool queues = pl.defer_search();
+#ifdef BC_LOG_LOOP
+  // (a log-mode specialised kernel: always.  With the tile number in a vector register the loop over the tiles is a divergent
+  // one to the compiler -- every `tile is full`, `lines were requested` becomes a 64-bit lane mask that lives across
+  // the stages -- and the split loop below then needs 131 vector registers)
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+#else
   const uint32_t wave = queues ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) : tid >> 6;
+#endif
   if (tid < kNCounters) s_cnt[tid] = 0;
 
   const bool with_qual = pl.quality_on && !(pl.abl() & 0x8u);
@@ -878,7 +910,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     ops.abl_ = pl.abl();
   }
   // flags bit 2: the workgroup's hot-counter cache sits between the tables and the tiles
-  const bool hot = (flags & 4u) != 0u;
+  const bool hot = JIT_HOT >= 0 ? JIT_HOT != 0 : (flags & 4u) != 0u;
   const uint32_t hot_seed = blockIdx.x * 0x85EBCA6Bu;
   uint32_t* hot_tag = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(smem) + lhash_vec * 16u);
   uint32_t* hot_cnt = hot_tag + kHotSlots;
@@ -921,12 +953,24 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   // during the locate stage -- until the quality stage has summed its runs and the table gathers that were in flight
   // beside it are consumed, then seq(t+1), landing while the verdicts are drawn and the tile is counted.  Nothing of
   // tile t+1 is requested before tile t's quality stage is over.
-  const uint64_t n_tiles = (n_reads + 63u) >> 6;
-  const uint64_t n_full = n_reads >> 6;  // tiles with all 64 reads
-  const uint64_t n_waves = (uint64_t)gridDim.x * (kTPB / 64);
+  const tile_t n_tiles = (tile_t)((n_reads + 63u) >> 6);
+  const tile_t n_full = (tile_t)(n_reads >> 6);  // tiles with all 64 reads
+  const tile_t n_waves = (tile_t)gridDim.x * (kTPB / 64);
+  // byte offset of a tile's lines in the batch: a multiple of 64 bytes, so 16-byte aligned
+  auto tile_off = [&](tile_t x) -> uint64_t {
+#ifdef BC_LOG_LOOP
+    return (uint64_t)x * full_bytes;  // (one 32 x 32 -> 64 bit multiply by an immediate)
+#else
+    return (x << 6) * stride;
+#endif
+  };
   uint32_t acc_cnt[kNCounters];
 #pragma unroll
   for (int k = 0; k < kNCounters; ++k) acc_cnt[k] = 0;
+#ifdef BC_LOG_LOOP
+  uint64_t pk_cnt = 0;    // the lane's packed outcome counters and the tiles they cover
+  uint32_t pk_tiles = 0;
+#endif
   // slack bytes behind the reads that the lane code may touch: plain values, written once
   // (a shared region keeps 'A' for both: a base to the pack, a plain score to the quality stage, which never
   // evaluates a run that reaches past its read)
@@ -945,16 +989,16 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
   // Log mode (`count_log` given: dense plans with a bit map and 32-bit indexes): no counting atomic at all.  Every read
   // of the batch gets one slot, written with one coalesced store per wave-tile -- its dense index when it is counted
   // here, kLogNone otherwise -- and the fold kernels (bc_fold.h) apply the log to bit map + table after the kernel.
-  const bool logm = count_log != nullptr;
+  const bool logm = JIT_COUNT == 1 ? true : (JIT_COUNT == 2 ? false : count_log != nullptr);
   uint32_t first_old = 0, first_on = 0, direct_tiles = 0;
   uint64_t first_idx = 0;
-  uint64_t t = (uint64_t)blockIdx.x * (kTPB / 64) + wave;
+  tile_t t = (tile_t)blockIdx.x * (kTPB / 64) + wave;
   bool seq_ready = false, qual_ready = false;  // requested ahead of time
   if (t < n_full && pipe) {
-    dma_tile(ops.tile, seq + (t << 6) * stride, full_bytes, lane);
+    dma_tile(ops.tile, seq + tile_off(t), full_bytes, lane);
     seq_ready = true;
     if (with_qual && !share) {
-      dma_tile(ops.qtile, qual + (t << 6) * stride, full_bytes, lane);
+      dma_tile(ops.qtile, qual + tile_off(t), full_bytes, lane);
       qual_ready = true;
     }
   }
@@ -987,25 +1031,41 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     }
     return add;
   };
+  // One tile.  kKind 1: a full tile whose lines were requested ahead of time; 2: a tile staged on demand (the partial
+  // last one, every tile of an unpipelined launch) -- what the wave's state says is then known when the kernel is
+  // compiled; 0: as the state says (the generic kernel).
+#ifdef BC_LOG_LOOP
+  auto tile_body = [&](auto kind_c) __attribute__((always_inline)) {
+    constexpr int kKind = decltype(kind_c)::value;
+#else
   for (; t < n_tiles; t += n_waves) {
-    const uint64_t wfirst = t << 6;
+    constexpr int kKind = 0;  // (one loop: the generic kernel, and the specialised kernels of the atomic path)
+#endif
+    const uint64_t wfirst = (uint64_t)t << 6;
+#ifdef BC_LOG_LOOP
+    // (t < n_tiles: the one tile behind the full ones is partial)
+    const uint32_t n_w = (kKind == 1 || t < n_full) ? 64u : (uint32_t)n_reads & 63u;
+#else
     const uint32_t n_w = n_reads - wfirst < 64u ? (uint32_t)(n_reads - wfirst) : 64u;
-    const uint64_t goff = wfirst * stride;  // multiple of 64 bytes: 16-byte aligned
-    const uint64_t tn = t + n_waves;
+#endif
+    const uint64_t goff = tile_off(t);
+    const tile_t tn = t + n_waves;
     const bool next_full = tn < n_full && pipe;
     ops.qsrc = qual + goff;
     ops.bytes = n_w * stride;
-    ops.next_seq = next_full ? seq + (tn << 6) * stride : nullptr;
+    ops.next_seq = next_full ? seq + tile_off(tn) : nullptr;
     // (shared region: a full tile whose sequence lines came ahead of time gets its quality lines the same way, in-tile)
-    ops.qual_async = share ? seq_ready : qual_ready;
-    if (seq_ready) {
+    const bool seq_here = kKind == 1 ? true : (kKind == 2 ? false : seq_ready);
+    const bool qual_here = kKind == 1 ? (with_qual && !share) : (kKind == 2 ? false : qual_ready);
+    ops.qual_async = share ? seq_here : qual_here;
+    if (seq_here) {
       // outstanding, oldest first: [this tile's sequence lines] [its quality lines] [the previous tile's
       // counter atomic] -- only the first must have landed.  Shared region: [this tile's sequence lines] [whatever
       // the previous tile issued after its quality stage and has consumed since] [its log store or counter atomic]
       // (qual_ready stays false).  The count must not exceed what was really issued after seq(t), or the last chunks
       // of seq(t) could be read before they land: pending_add counts one log store -- a tile that requested a next
       // one is full, so the store under `if (active)` has lanes and is issued -- or atomics issued under a wave vote.
-      wait_vm_keep((qual_ready ? ops.chunks : 0u) + ops.pending_add);
+      wait_vm_keep((qual_here ? ops.chunks : 0u) + ops.pending_add);
       wave_lds_fence();
     } else {
       wave_lds_fence();  // the previous tile's last LDS reads are done before the tile is overwritten
@@ -1048,11 +1108,28 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
         outcome = kDuplicate;
     }
     // outcome counters (SequenceErrors, info.rs:16-139)
+#ifdef BC_LOG_LOOP
+    // (per lane, in packed fields: bc_device_plan.h outcome_pack; added up before a field could overflow and with the
+    // wave's last tile)
+    pk_cnt += outcome_pack(active, outcome);
+    if (++pk_tiles == kPackTiles || tn >= n_tiles) {
+      uint32_t w[4];
+      outcome_split(pk_cnt, w);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) w[j] += (uint32_t)__shfl_xor((int)w[j], o);
+      outcome_fold(w, acc_cnt);
+      pk_cnt = 0;
+      pk_tiles = 0;
+    }
+#else
 #pragma unroll
     for (uint32_t k = 0; k < kNCounters; ++k) {
       if (k == kTotalReads) continue;
       acc_cnt[k] += (uint32_t)__popcll(__ballot(active && outcome == k));
     }
+#endif
     acc_cnt[kTotalReads] += n_w;
     if (trace_outcome && active && !(queues && outcome == kPending)) {
       trace_outcome[wfirst + lane] = (uint8_t)outcome;
@@ -1072,7 +1149,7 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
     qual_ready = false;
     if (next_full && with_qual && !share) {
       wave_lds_fence();
-      dma_tile(ops.qtile, qual + (tn << 6) * stride, full_bytes, lane);
+      dma_tile(ops.qtile, qual + tile_off(tn), full_bytes, lane);
       qual_ready = true;
     }
     // Results::add_count (info.rs:761-767): one no-return atomic into the dense counter table, or,
@@ -1197,7 +1274,17 @@ __device__ __forceinline__ void match_count_body(const DevPlan& pl, const uint8_
       }
       ++tile_seq;
     }
+#ifndef BC_LOG_LOOP
   }
+#else
+  };
+  // The log-mode specialised kernel's loop is split by tile kind.  Its fetch is pipelined or not for the whole launch (flags bit 0),
+  // so a tile was requested ahead of time exactly when it is full and the fetch is pipelined: the wave's first one
+  // above, every later one by the iteration before it (next_full).  The main loop carries neither the byte-wise fill
+  // nor a lane that has no read; the wave's partial tile, if it has it, follows.
+  for (const tile_t n_ahead = pipe ? n_full : 0u; t < n_ahead; t += n_waves) tile_body(TileKind<1>{});
+  for (; t < n_tiles; t += n_waves) tile_body(TileKind<2>{});
+#endif
   if (bits && first_on != 0u && ((first_old >> ((uint32_t)first_idx & 31u)) & 1u) != 0u) table_add_marked(pl, table, bits, first_idx);
 #ifdef BC_PROFILE
   if (lane == 0)
