@@ -14,17 +14,11 @@
 #include <vector>
 
 #include "../../include/barcode_count_hip.h"
+#include "bc_engine_impl.h"  // the bc_internal_* hooks (not part of the documented ABI)
 #include "bc_exchange.hpp"
 #include "bc_plan.hpp"
 
 using namespace bc;
-
-extern "C" {  // bc_engine.hip (not part of the documented ABI)
-void* bc_internal_table_unfolded(bc_engine* e, const void** bits);
-int bc_internal_table_now_plain(bc_engine* e);
-int bc_internal_table_pack_u8(const void* d_table_u32, const void* d_bits, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64,
-                              void* d_ovf_val_u32, uint64_t ovf_capacity, uint64_t* n_ovf, int device_id, void* hip_stream);
-}
 
 #define HIPC(expr)                                                                   \
   do {                                                                               \

@@ -6,6 +6,10 @@
 // LDS with 16-byte coalesced loads, outcome counters reduced per workgroup, one no-return
 // global atomic per matched read into the dense (sample, barcode tuple) counter table that
 // stands in for Results' nested HashMap (info.rs:661-665).
+//
+// This file is the hot path: the generic match kernels and their launch, log-mode counting and the owed reset, the
+// engine's creation, submits, sync and reset, and the small accessors.  The key tables are bc_keys.hip, the rows and
+// the dense enrichment bc_finish.hip, probes and table packing bc_probe.hip, the read generator bc_synth.hip.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stdio.h>
@@ -13,9 +17,7 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <functional>
 #include <thread>
-#include <unordered_map>
 #include <string>
 #include <vector>
 
@@ -23,10 +25,6 @@
 #include "bc_kernel.h"
 #include "bc_engine_impl.h"
 #include "bc_fold.h"
-#include "bc_synth.h"
-
-extern "C" int bc_internal_table_pack_u8(const void* d_table_u32, const void* d_bits, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64,
-                                         void* d_ovf_val_u32, uint64_t ovf_capacity, uint64_t* n_ovf, int device_id, void* hip_stream);
 
 namespace bc {
 
@@ -124,148 +122,6 @@ __global__ __launch_bounds__(256) void long_match_kernel(const LongPlan* __restr
   }
 }
 
-// ---- tables of wide keys (bc_long.h): W words per slot + a ready flag; ONE lane of a wavefront inserts at a time ----
-// keys[i * W ..] (+ vals[i], or 1 for every key when vals is null and count_ones, or nothing) into the table; *n_new
-// counts the keys that were not there.  zero_from / zero_bits: payload bits cleared before the insert (with the
-// fingerprint recomputed) -- the random barcode's planes, when the table being built is the per-tuple aggregate.
-__global__ void wide_insert_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ src_ready,
-                                   const uint32_t* __restrict__ src_vals, uint64_t n, uint32_t W,
-                                   unsigned long long* __restrict__ slots, uint32_t* __restrict__ ready, uint32_t* __restrict__ vals,
-                                   uint64_t mask, int add_one, uint32_t zero_from, uint32_t zero_bits,
-                                   unsigned long long* __restrict__ n_new) {
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  uint32_t fresh = 0;
-  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
-    const uint64_t i = base + threadIdx.x;
-    const bool have = i < n && (!src_ready || src_ready[i] != 0u);  // (a source table: only its published slots)
-    unsigned long long todo = __ballot(have);
-    while (todo) {
-      const unsigned l = (unsigned)__ffsll((long long)todo) - 1u;
-      todo &= todo - 1ull;
-      if (__lane_id() == l) {
-        uint64_t key[kMaxKeyWords];
-        for (uint32_t w = 0; w < W; ++w) key[w] = keys[i * W + w];
-        if (zero_bits) {
-          for (uint32_t b = zero_from; b < zero_from + zero_bits; ++b) key[1u + (b >> 6)] &= ~(1ull << (b & 63u));
-          key[0] = wide_fingerprint(key, W);
-        }
-        bool is_new;
-        const uint64_t slot = wide_find_or_insert(slots, ready, mask, W, key, is_new);
-        fresh += is_new ? 1u : 0u;
-        if (vals) atomicAdd(&vals[slot], src_vals ? src_vals[i] : (add_one ? 1u : 0u));
-      }
-    }
-  }
-  if (n_new && fresh) atomicAdd(n_new, (unsigned long long)fresh);
-}
-
-// the published slots of a table, densely: keys (W words each) and counts
-__global__ void wide_export_kernel(const unsigned long long* __restrict__ slots, const uint32_t* __restrict__ ready,
-                                   const uint32_t* __restrict__ vals, uint64_t n, uint32_t W, unsigned long long* cursor,
-                                   unsigned long long* __restrict__ out_keys, uint32_t* __restrict__ out_vals, uint64_t capacity) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    if (ready[i] == 0u) continue;
-    if (vals && out_vals && vals[i] == 0u) continue;  // (a key whose count was discarded never shows)
-    const unsigned long long p = atomicAdd(cursor, 1ull);
-    if (p < capacity) {
-      if (out_keys)
-        for (uint32_t w = 0; w < W; ++w) out_keys[p * W + w] = slots[i * W + w];
-      if (out_vals) out_vals[p] = vals ? vals[i] : 1u;
-    }
-  }
-}
-
-// dense u32 counts -> one byte each (what fits) + a list of the rest: the form in which tables travel
-// between GPUs (most counts of a DEL run are small, and a quarter of the bytes is a quarter of the time
-// on a link)
-// (bits, may be NULL: two-level counting not folded -- the count of entry i is table[i] + bit i; reading both here
-// spares the exchange a fold pass over the whole table)
-__global__ void table_pack_u8_kernel(const uint32_t* __restrict__ table, const uint32_t* __restrict__ bits, uint64_t n,
-                                     uint8_t* __restrict__ out, unsigned long long* cursor,
-                                     unsigned long long* __restrict__ ovf_idx, uint32_t* __restrict__ ovf_val, uint64_t capacity) {
-  const uint64_t n4 = n >> 2;
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n4; i += step) {  // four counts in, four bytes out
-    const uint4 v = reinterpret_cast<const uint4*>(table)[i];
-    const uint32_t four = bits ? (bits[i >> 3] >> ((uint32_t)(i & 7u) * 4u)) & 15u : 0u;
-    const uint32_t c[4] = {v.x + (four & 1u), v.y + ((four >> 1) & 1u), v.z + ((four >> 2) & 1u), v.w + (four >> 3)};
-    uint32_t packed = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (c[k] <= 255u) {
-        packed |= c[k] << (8 * k);
-      } else {
-        const unsigned long long p = atomicAdd(cursor, 1ull);
-        if (p < capacity) {
-          ovf_idx[p] = i * 4 + k;
-          ovf_val[p] = c[k];
-        }
-      }
-    }
-    reinterpret_cast<uint32_t*>(out)[i] = packed;
-  }
-  for (i = (n4 << 2) + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const uint32_t c = table[i] + (bits ? (bits[i >> 5] >> (i & 31)) & 1u : 0u);
-    if (c <= 255u) {
-      out[i] = (uint8_t)c;
-    } else {
-      out[i] = 0;
-      const unsigned long long p = atomicAdd(cursor, 1ull);
-      if (p < capacity) {
-        ovf_idx[p] = i;
-        ovf_val[p] = c;
-      }
-    }
-  }
-}
-
-// the receiving side: out[i] = sum over the `rows` byte slices of row[r][i]  (i < n, n a multiple of 4)
-__global__ void table_sum_u8_kernel(const uint8_t* __restrict__ rows, uint32_t n_rows, uint64_t n, uint32_t* __restrict__ out) {
-  const uint64_t n4 = n >> 2;
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n4; i += step) {
-    uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    for (uint32_t r = 0; r < n_rows; ++r) {
-      const uint32_t v = reinterpret_cast<const uint32_t*>(rows + (uint64_t)r * n)[i];
-      a0 += v & 0xFFu;
-      a1 += (v >> 8) & 0xFFu;
-      a2 += (v >> 16) & 0xFFu;
-      a3 += v >> 24;
-    }
-    reinterpret_cast<uint4*>(out)[i] = make_uint4(a0, a1, a2, a3);
-  }
-}
-
-// box diagnostic: no-return atomic adds of `delta` to random counters of a table -- the rate the memory system
-// sustains for the match kernel's counting alone (bc_probe_atomic_rate: one pass of +1, one of -1 over the same
-// addresses, so the counts end as they were)
-__global__ void atomic_probe_kernel(uint32_t* table, uint64_t entries, uint32_t per, uint64_t seed, uint32_t delta) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (uint32_t i = 0; i < per; ++i) atomicAdd(&table[hash64(seed + t * per + i) % entries], delta);
-}
-
-// shader clock probe: one wave spins for ~0.3 ms and reports (shader clock ticks, 100 MHz reference ticks)
-__global__ void sclk_probe_kernel(unsigned long long* out) {
-  const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
-  const unsigned long long c0 = __builtin_readcyclecounter();
-  unsigned long long r1 = r0;
-  uint32_t x = threadIdx.x;
-  while (r1 - r0 < 30000ull) {  // 0.3 ms at 100 MHz
-    for (int i = 0; i < 256; ++i) x = x * 1664525u + 1013904223u;
-    r1 = __builtin_amdgcn_s_memrealtime();
-  }
-  const unsigned long long c1 = __builtin_readcyclecounter();
-  if (threadIdx.x == 0) {
-    out[0] = c1 - c0;
-    out[1] = r1 - r0;
-    out[2] = x;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // plan-time kernels
 // ------------------------------------------------------------------------------------------------
@@ -278,124 +134,12 @@ __global__ void build_dtable_kernel(const DevPlan* __restrict__ plp, uint32_t g,
   out[q] = dtable_entry(G, q);
 }
 
-// bc_fix_error: one wavefront, one query, plain fix_error semantics (no exact-member shortcut)
+// bc_fix_error (bc_probe.hip): one wavefront, one query, plain fix_error semantics (no exact-member shortcut).  It
+// lives beside the match kernels, the other users of wave_fix_error: compiled on its own it comes out register for
+// register different.
 __global__ void fix_error_kernel(DevGroup G, uint32_t q1, uint32_t q2, uint32_t qn, uint32_t qx, uint32_t* out) {
   const uint32_t r = wave_fix_error(G, q1, q2, qn, qx, false);
   if (threadIdx.x == 0) *out = r;
-}
-
-__global__ void set_fill_kernel(unsigned long long* slots, uint64_t n) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) slots[i] = kEmptyKey;
-}
-
-// re-inserts every key of `src` (n slots, or n plain keys when `dense`) into dst; counts the new ones
-__global__ void set_insert_kernel(const unsigned long long* __restrict__ src, uint64_t n, unsigned long long* dst,
-                                  uint64_t dmask, unsigned long long* n_new) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  uint32_t c = 0;
-  for (; i < n; i += step) {
-    const unsigned long long k = src[i];
-    if (k != kEmptyKey && set_insert(dst, dmask, k)) ++c;
-  }
-  if (n_new) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
-    if (__lane_id() == 0 && c) atomicAdd(n_new, (unsigned long long)c);
-  }
-}
-
-// moves (key, value) pairs into a larger map
-__global__ void map_rehash_kernel(const unsigned long long* __restrict__ src, const uint32_t* __restrict__ src_vals,
-                                  uint64_t n, unsigned long long* dst, uint32_t* dst_vals, uint64_t dmask) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = src[i];
-    if (k != kEmptyKey) atomicAdd(&dst_vals[map_slot(dst, dmask, k)], src_vals[i]);
-  }
-}
-
-// raw captures + random barcode: count of a tuple = number of its distinct (tuple, random) keys
-__global__ void set_to_map_kernel(const unsigned long long* __restrict__ slots, uint64_t n, uint64_t rspace,
-                                  unsigned long long* dst, uint32_t* dst_vals, uint64_t dmask) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = slots[i];
-    if (k != kEmptyKey) atomicAdd(&dst_vals[map_slot(dst, dmask, k / rspace)], 1u);
-  }
-}
-
-__global__ void map_export_kernel(const unsigned long long* __restrict__ slots, const uint32_t* __restrict__ vals,
-                                  uint64_t n, unsigned long long* cursor, uint64_t* __restrict__ out_key,
-                                  uint32_t* __restrict__ out_cnt) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = slots[i];
-    if (k != kEmptyKey) {
-      const unsigned long long p = atomicAdd(cursor, 1ull);
-      out_key[p] = k;
-      out_cnt[p] = vals[i];
-    }
-  }
-}
-
-// adds (key, count) pairs into a map
-__global__ void map_add_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ cnts, uint64_t n,
-                               unsigned long long* dst, uint32_t* dst_vals, uint64_t dmask) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = keys[i];
-    if (k != kEmptyKey && cnts[i]) atomicAdd(&dst_vals[map_slot(dst, dmask, k)], cnts[i]);
-  }
-}
-
-// counts the occupied slots with a non-zero value / writes them out (capacity-checked)
-__global__ void map_export_checked_kernel(const unsigned long long* __restrict__ slots, const uint32_t* __restrict__ vals,
-                                          uint64_t n, unsigned long long* cursor, unsigned long long* __restrict__ out_key,
-                                          uint32_t* __restrict__ out_cnt, uint64_t capacity) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = slots[i];
-    if (k != kEmptyKey && vals[i]) {
-      const unsigned long long p = atomicAdd(cursor, 1ull);
-      if (p < capacity) {
-        out_key[p] = k;
-        out_cnt[p] = vals[i];
-      }
-    }
-  }
-}
-
-// compacts the keys of a set into out[0 .. *cursor)
-__global__ void set_export_kernel(const unsigned long long* __restrict__ slots, uint64_t n, unsigned long long* cursor,
-                                  unsigned long long* __restrict__ out, uint64_t capacity) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = slots[i];
-    if (k != kEmptyKey) {
-      const unsigned long long p = atomicAdd(cursor, 1ull);
-      if (p < capacity) out[p] = k;
-    }
-  }
-}
-
-// final counts with a random barcode = number of distinct random barcodes per tuple (output.rs:265-270)
-__global__ void set_to_table_kernel(const unsigned long long* __restrict__ slots, uint64_t n, uint64_t rspace,
-                                    uint32_t* __restrict__ table) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const unsigned long long k = slots[i];
-    if (k != kEmptyKey) atomicAdd(&table[k / rspace], 1u);
-  }
 }
 
 // Two-level counting (bc_kernel.h): count = bit + table entry.  Folds the bits into the table (one add per set bit, in
@@ -468,80 +212,9 @@ __global__ void sparse_reset_kernel(uint32_t* __restrict__ table, uint4* __restr
   }
 }
 
-// Compaction of the dense table into sparse rows (bc_engine_finish), in two bounded passes.  bits may be NULL; with
-// two-level counting the count of entry i is table[i] + bit i: read here as they stand, so an engine-owned table never
-// needs the fold pass.
-// Pass 1: non-zero entries per block of `block` consecutive entries (one workgroup per block, grid-stride).
-__global__ void count_blocks_kernel(const uint32_t* __restrict__ table, const uint32_t* __restrict__ bits, uint64_t n,
-                                    uint64_t block, uint64_t n_blocks, uint32_t* __restrict__ per_block) {
-  __shared__ uint32_t part[4];
-  for (uint64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-    const uint64_t lo = b * block, hi = (lo + block < n) ? lo + block : n;
-    uint32_t c = 0;
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-      c += (table[i] | (bits ? (bits[i >> 5] >> (i & 31)) & 1u : 0u)) != 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) per_block[b] = part[0] + part[1] + part[2] + part[3];
-    __syncthreads();
-  }
-}
-
-// Pass 2: the rows of entries [lo, hi) into a staging buffer the host has sized from pass 1 (one cursor add per
-// wavefront; the rows of one range come out in no particular order).
-__global__ void compact_range_kernel(const uint32_t* __restrict__ table, const uint32_t* __restrict__ bits, uint64_t lo,
-                                     uint64_t hi, unsigned long long* cursor, uint64_t capacity,
-                                     uint64_t* __restrict__ out_idx, uint32_t* __restrict__ out_cnt) {
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  // (every lane of a wavefront runs the same number of rounds: the ballot below needs them all)
-  for (uint64_t base = lo + (uint64_t)blockIdx.x * blockDim.x; base < hi; base += step) {
-    const uint64_t i = base + threadIdx.x;
-    uint32_t v = 0;
-    if (i < hi) v = table[i] + (bits ? (bits[i >> 5] >> (i & 31)) & 1u : 0u);
-    const unsigned long long m = __ballot(v != 0u);
-    if (m == 0ull) continue;
-    unsigned long long first = 0;
-    if (__lane_id() == 0) first = atomicAdd(cursor, (unsigned long long)__popcll(m));
-    first = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(first >> 32)) << 32) |
-            (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)first);
-    if (v) {
-      const unsigned long long p = first + __popcll(m & ((1ull << __lane_id()) - 1ull));
-      if (p < capacity) {  // (cannot fail while pass 1 and pass 2 see the same table; a guard, not a path)
-        out_idx[p] = i;
-        out_cnt[p] = v;
-      }
-    }
-  }
-}
-
-__global__ void synth_kernel(SynthDev S, uint64_t first, uint64_t n, uint8_t* __restrict__ seq,
-                             uint8_t* __restrict__ qual, uint32_t stride) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const uint64_t i = first + t;
-  SynthRead R;
-  synth_begin(S, i, R);
-  uint8_t* so = seq + t * stride;
-  uint8_t* qo = qual ? qual + t * stride : nullptr;
-  for (uint32_t p = 0; p < S.read_len; ++p) {
-    uint8_t b, q;
-    synth_byte(S, i, R, p, b, q);
-    so[p] = b;
-    if (qo) qo[p] = q;
-  }
-  for (uint32_t p = S.read_len; p < stride; ++p) {
-    so[p] = '\n';
-    if (qo) qo[p] = '\n';
-  }
-}
-
 }  // namespace bc
 
 using namespace bc;
-
-static void counts_changed(bc_engine* e) { ++e->counts_epoch; }
 
 int bc::upload(bc_engine* e, const void* src, size_t bytes, uint64_t* out) {
   void* d = nullptr;
@@ -887,7 +560,7 @@ static int settle_bits_on(bc_engine* e, hipStream_t st) {
   return BC_OK;
 }
 // Everything owed, on the engine's stream: first thing in every path that reads or writes table, dirty map or bit map.
-static int settle_owed(bc_engine* e) {
+int bc::settle_owed(bc_engine* e) {
   int rc = settle_table_on(e, e->stream);
   if (rc == BC_OK) rc = settle_bits_on(e, e->stream);
   return rc;
@@ -942,6 +615,38 @@ static int fork_owed(bc_engine* e, const OwedPlan& plan, bool* join) {
   return rc;
 }
 
+// Times one launch sequence when bc_engine_timing is on: created and recorded at construction (rc: how that went),
+// done() records the end and hands the pair to e->events; a pair that was not handed over is destroyed.
+struct LaunchTimer {
+  bc_engine* e;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t rc = hipSuccess;
+  explicit LaunchTimer(bc_engine* e_) : e(e_) {
+    if (!e->timing) return;
+    if ((rc = hipEventCreate(&e0)) == hipSuccess && (rc = hipEventCreate(&e1)) == hipSuccess) rc = hipEventRecord(e0, e->stream);
+  }
+  hipError_t done() {
+    if (!e1) return hipSuccess;
+    const hipError_t end = hipEventRecord(e1, e->stream);
+    if (end == hipSuccess) {
+      e->events.emplace_back(e0, e1);
+      e0 = e1 = nullptr;
+    }
+    return end;
+  }
+  ~LaunchTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+static uint64_t slot_mask(const bc_engine* e) { return e->n_slots ? e->n_slots - 1 : 0; }
+
+// the flags word of a match kernel, generic or specialised: `tables` and `hot` are that kernel's fields of the MatchShape
+static uint32_t match_flags(const MatchShape& s, bool tables, bool hot) {
+  return (s.pipe ? 1u : 0u) | (tables ? 2u : 0u) | (hot ? 4u : 0u);
+}
+
 // s: match_shape() of the batch; NW = s.generic_nw
 template <int NW, int NWW>
 static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
@@ -965,7 +670,7 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     const int rc = settle_bits_on(e, e->stream);
     if (rc != BC_OK) return rc;
   }
-  const uint32_t flags = (s.pipe ? 1u : 0u) | (s.tables_generic ? 2u : 0u) | (s.hot_generic && hot_on ? 4u : 0u);
+  const uint32_t flags = match_flags(s, s.tables_generic, s.hot_generic && hot_on);
   if (s.lds + 64 > e->lds_limit) {
     set_error("read stride too large for one LDS tile");
     return BC_ERR_UNSUPPORTED;
@@ -981,12 +686,8 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   const uint64_t resident = (uint64_t)per_cu * e->n_cus;
   const uint64_t blocks = std::min<uint64_t>((n_reads + kTPB - 1) / kTPB, resident);
   uint64_t blocks_jit = blocks, resident_jit = resident;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (e->timing) {
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, e->stream));
-  }
+  LaunchTimer timer(e);
+  HIP_TRY(timer.rc);
   hipFunction_t jit_fn = nullptr;
   e->reads_seen += n_reads;
   // (a log-mode specialised kernel numbers its tiles in 32 bits, bc_kernel.h tile_t: log_chunk is 2^27 reads at most)
@@ -1027,11 +728,10 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     uint8_t* a_to = e->trace_outcome ? e->trace_outcome + trace_off + c0 : nullptr;
     uint64_t* a_ti = e->trace_idx ? e->trace_idx + trace_off + c0 : nullptr;
     uint32_t* a_log = use_log ? e->d_log : nullptr;
-    uint64_t a_n = n_c;
+    uint64_t a_n = n_c, a_smask = slot_mask(e);
+    uint32_t a_region = s.region;
     if (jit_fn) {
-      uint32_t a_region = s.region;
-      uint64_t a_smask = e->n_slots ? e->n_slots - 1 : 0;
-      uint32_t a_flags = (s.pipe ? 1u : 0u) | (s.tables_jit ? 2u : 0u) | (s.hot_jit && hot_on ? 4u : 0u);
+      uint32_t a_flags = match_flags(s, s.tables_jit, s.hot_jit && hot_on);
       void* args[] = {&a_seq, &a_qual, &a_lens, &a_qlens, &stride, &read_len, &nd, &a_n, &a_region, &e->d_table, &e->d_bits, &e->d_slots,
                       &e->d_vals, &a_smask, &e->d_counters, &a_to, &a_ti, &a_flags, &a_log,
                       &e->d_ready};  // (the last one: the kernel of a wide-key plan only, bc_jit.hip jit_source)
@@ -1041,12 +741,12 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
       const uint64_t grid = std::min<uint64_t>(blocks, (n_c + kTPB - 1) / kTPB);
       if (wide)
         hipLaunchKernelGGL((match_count_wide_kernel<NW, NWW>), dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual,
-                           a_lens, a_qlens, stride, read_len, nd, a_n, s.region, e->d_slots, e->d_vals, e->d_ready,
-                           e->n_slots ? e->n_slots - 1 : 0, e->d_counters, a_to, a_ti, flags);
+                           a_lens, a_qlens, stride, read_len, nd, a_n, a_region, e->d_slots, e->d_vals, e->d_ready, a_smask,
+                           e->d_counters, a_to, a_ti, flags);
       else
         hipLaunchKernelGGL((match_count_kernel<NW, NWW>), dim3((uint32_t)grid), dim3(kTPB), lds, e->stream, e->d_plan, a_seq, a_qual, a_lens,
-                           a_qlens, stride, read_len, nd, a_n, s.region, e->d_table, e->d_bits, e->d_slots, e->d_vals,
-                           e->n_slots ? e->n_slots - 1 : 0, e->d_counters, a_to, a_ti, flags, a_log);
+                           a_qlens, stride, read_len, nd, a_n, a_region, e->d_table, e->d_bits, e->d_slots, e->d_vals, a_smask,
+                           e->d_counters, a_to, a_ti, flags, a_log);
     }
     HIP_TRY(hipGetLastError());
     if (use_log) {
@@ -1071,10 +771,7 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
   e->last_lds = jit_fn ? lds_jit : lds;
   e->last_grid = (uint32_t)std::min<uint64_t>(jit_fn ? blocks_jit : blocks, (std::min<uint64_t>(chunk, n_reads) + kTPB - 1) / kTPB);
   e->last_resident = (uint32_t)(jit_fn ? resident_jit : resident);
-  if (e->timing) {
-    HIP_TRY(hipEventRecord(e1, e->stream));
-    e->events.emplace_back(e0, e1);
-  }
+  HIP_TRY(timer.done());
   return BC_OK;
 }
 
@@ -1105,79 +802,26 @@ static int launch_long(bc_engine* e, const void* d_seq, const void* d_qual, cons
   int rc = ensure_long(e);
   if (rc != BC_OK) return rc;
   if ((rc = settle_owed(e)) != BC_OK) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (e->timing) {
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, e->stream));
-  }
+  LaunchTimer timer(e);
+  HIP_TRY(timer.rc);
   // four wavefronts per workgroup, one read per wavefront and step; enough workgroups to fill the chip
   const uint64_t blocks = std::min<uint64_t>((n_reads + 3) / 4, (uint64_t)e->n_cus * 8);
   hipLaunchKernelGGL(long_match_kernel, dim3((uint32_t)blocks), dim3(256), 0, e->stream, e->d_long, (const uint8_t*)d_seq,
                      (const uint8_t*)d_qual, (const uint16_t*)d_lens, (const uint16_t*)d_qlens, stride, read_len, n_reads,
-                     e->d_table, e->d_slots, e->d_vals, e->d_ready, e->n_slots ? e->n_slots - 1 : 0, e->d_counters,
+                     e->d_table, e->d_slots, e->d_vals, e->d_ready, slot_mask(e), e->d_counters,
                      e->trace_outcome ? e->trace_outcome + trace_off : nullptr, e->trace_idx ? e->trace_idx + trace_off : nullptr);
   HIP_TRY(hipGetLastError());
   e->table_all_dirty = true;  // (this kernel adds to the table without flagging blocks)
   e->last_kernel = "long_match_kernel";
   e->reads_seen += n_reads;
-  if (e->timing) {
-    HIP_TRY(hipEventRecord(e1, e->stream));
-    e->events.emplace_back(e0, e1);
-  }
+  HIP_TRY(timer.done());
   return BC_OK;
 }
 
 uint32_t bc::grid_for(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 256ull * 32); }
 
-// Random-barcode mode: keeps the hash set at most half full for `more` further keys.  Growing
-// allocates a set of twice the size (or more) and re-inserts the old keys on the device.
-static int set_reserve(bc_engine* e, uint64_t more) {
-  const DevPlan& P = e->h.plan;
-  if (!P.has_random && !P.sparse) return BC_OK;
-  const bool with_vals = P.sparse && !P.has_random;
-  const uint32_t W = e->key_words;
-  e->key_bound += more;
-  uint64_t want = 1ull << 20;
-  while (want < 2 * e->key_bound) want <<= 1;
-  if (want <= e->n_slots) return BC_OK;
-  unsigned long long* fresh = nullptr;
-  uint32_t* fresh_vals = nullptr;
-  uint32_t* fresh_ready = nullptr;
-  ScratchGuard g;  // (what is allocated here is released on an early return, and handed over at the end)
-  HIP_TRY(g.dmalloc(&fresh, want * W * 8));
-  hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(want * W)), dim3(256), 0, e->stream, fresh, want * W);
-  if (with_vals) {
-    HIP_TRY(g.dmalloc(&fresh_vals, want * 4));
-    HIP_TRY(hipMemsetAsync(fresh_vals, 0, want * 4, e->stream));
-  }
-  if (W > 1) {
-    HIP_TRY(g.dmalloc(&fresh_ready, want * 4));
-    HIP_TRY(hipMemsetAsync(fresh_ready, 0, want * 4, e->stream));
-  }
-  if (e->d_slots) {
-    if (W > 1)
-      hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_ready, e->d_vals,
-                         e->n_slots, W, fresh, fresh_ready, fresh_vals, want - 1, 0, 0u, 0u, (unsigned long long*)nullptr);
-    else if (with_vals)
-      hipLaunchKernelGGL(map_rehash_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_vals,
-                         e->n_slots, fresh, fresh_vals, want - 1);
-    else
-      hipLaunchKernelGGL(set_insert_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->n_slots,
-                         fresh, want - 1, (unsigned long long*)nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    (void)hipFree(e->d_slots);
-    if (e->d_vals) (void)hipFree(e->d_vals);
-    if (e->d_ready) (void)hipFree(e->d_ready);
-  }
-  HIP_TRY(hipGetLastError());
-  g.dev.clear();  // kept: the engine owns them now
-  e->d_slots = fresh;
-  e->d_vals = fresh_vals;
-  e->d_ready = fresh_ready;
-  e->n_slots = want;
-  return BC_OK;
+void bc::fix_error_launch(const DevGroup& G, uint32_t q1, uint32_t q2, uint32_t qn, uint32_t qx, uint32_t* d_out) {
+  hipLaunchKernelGGL(fix_error_kernel, dim3(1), dim3(64), 0, 0, G, q1, q2, qn, qx, d_out);
 }
 
 static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
@@ -1275,8 +919,10 @@ int bc_engine_device(const bc_engine* e) { return e->device; }
 uint32_t bc_engine_key_words(const bc_engine* e) { return e->key_words; }
 const bc_plan* bc_engine_plan(const bc_engine* e) { return e->src_plan; }
 
+}  // extern "C"
+
 // staging copy pageable -> pinned, cut into slices for a few threads: one core moves ~10 GB/s, the link takes ~50
-static void staged_copy(void* dst, const void* src, size_t n) {
+void bc::staged_copy(void* dst, const void* src, size_t n) {
   static const int threads = []() {
     const char* t = getenv("BC_STAGE_THREADS");
     const int v = t ? atoi(t) : 4;
@@ -1297,6 +943,8 @@ static void staged_copy(void* dst, const void* src, size_t n) {
   memcpy(dst, src, std::min(slice, n));
   for (auto& th : pool) th.join();
 }
+
+extern "C" {
 
 int bc_engine_submit_host(bc_engine* e, const void* seq, const void* qual, const uint16_t* lens, uint32_t stride,
                           uint32_t read_len, uint64_t n_reads) {
@@ -1425,16 +1073,7 @@ static int reset_impl(bc_engine* e, bool counters_too) {
   e->bits_dirty = false;
   e->reads_since_fold = 0;
   if (counters_too) HIP_TRY(hipMemsetAsync(e->d_counters, 0, BC_NCOUNTERS * 8, e->stream));
-  if (e->d_slots) {
-    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(e->n_slots * e->key_words)), dim3(256), 0, e->stream, e->d_slots,
-                       e->n_slots * e->key_words);
-    HIP_TRY(hipGetLastError());
-    if (e->d_vals) HIP_TRY(hipMemsetAsync(e->d_vals, 0, e->n_slots * 4, e->stream));
-    if (e->d_ready) HIP_TRY(hipMemsetAsync(e->d_ready, 0, e->n_slots * 4, e->stream));
-  }
-  e->key_bound = 0;
-  e->table_materialized = false;
-  return BC_OK;
+  return clear_key_table(e);
 }
 
 int bc_engine_counters(bc_engine* e, uint64_t out[BC_NCOUNTERS]) {
@@ -1505,788 +1144,10 @@ int bc_engine_trace(bc_engine* e, void* d_outcome_u8, void* d_index_u64) {
 
 }  // extern "C"
 
-int bc::export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** d_key, uint32_t** d_cnt, uint64_t* n_out) {
-  unsigned long long* keys = e->d_slots;
-  uint32_t* vals = e->d_vals;
-  const uint64_t n_slots = e->n_slots;
-  if (e->h.plan.has_random) {
-    // count of a tuple = number of its distinct random barcodes (output.rs:265-270)
-    unsigned long long* agg_keys = nullptr;
-    uint32_t* agg_vals = nullptr;
-    HIP_TRY(g.dmalloc(&agg_keys, n_slots * 8));
-    HIP_TRY(g.dmalloc(&agg_vals, n_slots * 4));
-    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, agg_keys, n_slots);
-    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
-    hipLaunchKernelGGL(set_to_map_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, n_slots,
-                       e->h.plan.rspace, agg_keys, agg_vals, n_slots - 1);
-    HIP_TRY(hipGetLastError());
-    keys = agg_keys;
-    vals = agg_vals;
-  }
-  unsigned long long* d_n = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  // upper bound on the rows: the keys held
-  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);
-  HIP_TRY(g.dmalloc(d_key, cap * 8));
-  HIP_TRY(g.dmalloc(d_cnt, cap * 4));
-  hipLaunchKernelGGL(map_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, vals, n_slots, d_n, *d_key,
-                     *d_cnt);
-  HIP_TRY(hipGetLastError());
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (n > cap) {  // (cannot happen: key_bound counts every insert)
-    set_error(std::string(who) + ": the key map holds more keys than its bound");
-    return BC_ERR_STATE;
-  }
-  *n_out = n;
-  return BC_OK;
-}
-
-// wide keys (bc_long.h): the two steps of export_pairs on slots of key_words words
-int bc::export_wide(bc_engine* e, const char* who, ScratchGuard& g, unsigned long long** d_key, uint32_t** d_cnt,
-                    uint64_t* n_out) {
-  const DevPlan& P = e->h.plan;
-  unsigned long long* keys = e->d_slots;
-  uint32_t* vals = e->d_vals;
-  const uint64_t n_slots = e->n_slots;
-  const uint32_t W = e->key_words;
-  const uint32_t* ready = e->d_ready;
-  ScratchGuard agg;  // the table of tuples: gone when the rows are out
-  if (P.has_random) {
-    // count of a tuple = number of its distinct random barcodes (output.rs:265-270): every key, its random
-    // barcode's planes cleared, into a map of tuples
-    unsigned long long* agg_keys = nullptr;
-    uint32_t *agg_vals = nullptr, *agg_ready = nullptr;
-    HIP_TRY(agg.dmalloc(&agg_keys, n_slots * W * 8));
-    HIP_TRY(agg.dmalloc(&agg_vals, n_slots * 4));
-    HIP_TRY(agg.dmalloc(&agg_ready, n_slots * 4));
-    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(n_slots * W)), dim3(256), 0, e->stream, agg_keys, n_slots * W);
-    HIP_TRY(hipMemsetAsync(agg_vals, 0, n_slots * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(agg_ready, 0, n_slots * 4, e->stream));
-    hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_ready,
-                       (const uint32_t*)nullptr, n_slots, W, agg_keys, agg_ready, agg_vals, n_slots - 1, 1, e->lh.plan.rnd_bit,
-                       3u * e->lh.plan.rnd_len, (unsigned long long*)nullptr);
-    HIP_TRY(hipGetLastError());
-    keys = agg_keys;
-    vals = agg_vals;
-    ready = agg_ready;
-  }
-  unsigned long long* d_n = nullptr;
-  HIP_TRY(agg.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  const uint64_t cap = std::min<uint64_t>(n_slots, e->key_bound ? e->key_bound : 1);
-  HIP_TRY(g.dmalloc(d_key, cap * W * 8));
-  HIP_TRY(g.dmalloc(d_cnt, cap * 4));
-  hipLaunchKernelGGL(wide_export_kernel, dim3(grid_for(n_slots)), dim3(256), 0, e->stream, keys, ready, vals, n_slots, W, d_n, *d_key,
-                     *d_cnt, cap);
-  HIP_TRY(hipGetLastError());
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (n > cap) {  // (cannot happen: key_bound counts every insert)
-    set_error(std::string(who) + ": the key map holds more keys than its bound");
-    return BC_ERR_STATE;
-  }
-  *n_out = n;
-  return BC_OK;
-}
-
 extern "C" {
-
-// rows of a sparse plan: (tuple key, count) pairs straight out of the hash map
-static int finish_sparse(bc_engine* e, uint64_t* n_rows) {
-  e->row_idx.clear();
-  e->row_cnt.clear();
-  if (n_rows) *n_rows = 0;
-  e->row_wide.clear();
-  if (!e->d_slots) return BC_OK;
-  ScratchGuard g;
-  if (e->key_words > 1) {
-    const uint32_t W = e->key_words;
-    unsigned long long* d_key = nullptr;
-    uint32_t* d_cnt = nullptr;
-    uint64_t n = 0;
-    const int rc = export_wide(e, "bc_engine_finish", g, &d_key, &d_cnt, &n);
-    if (rc != BC_OK) return rc;
-    try {
-      e->row_wide.resize(n * W);
-      e->row_cnt.resize(n);
-    } catch (const std::bad_alloc&) {
-      e->row_wide = std::vector<uint64_t>();
-      e->row_cnt = std::vector<uint32_t>();
-      set_error("bc_engine_finish: out of host memory for " + std::to_string(n) + " rows");
-      return BC_ERR_NOMEM;
-    }
-    if (n) {
-      HIP_TRY(hipMemcpy(e->row_wide.data(), d_key, n * W * 8, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(e->row_cnt.data(), d_cnt, n * 4, hipMemcpyDeviceToHost));
-    }
-    if (n_rows) *n_rows = n;
-    return BC_OK;
-  }
-  uint64_t* d_key = nullptr;
-  uint32_t* d_cnt = nullptr;
-  uint64_t n = 0;
-  const int rc = export_pairs(e, "bc_engine_finish", g, &d_key, &d_cnt, &n);
-  if (rc != BC_OK) return rc;
-  try {
-    e->row_idx.resize(n);
-    e->row_cnt.resize(n);
-  } catch (const std::bad_alloc&) {
-    e->row_idx = std::vector<uint64_t>();
-    e->row_cnt = std::vector<uint32_t>();
-    set_error("bc_engine_finish: out of host memory for " + std::to_string(n) + " rows");
-    return BC_ERR_NOMEM;
-  }
-  if (n) {
-    HIP_TRY(hipMemcpy(e->row_idx.data(), d_key, n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(e->row_cnt.data(), d_cnt, n * 4, hipMemcpyDeviceToHost));
-  }
-  if (n_rows) *n_rows = n;
-  return BC_OK;
-}
-
-// Dense table -> sparse rows in bounded memory: pass 1 counts the non-zero entries per block of the table, the host
-// groups consecutive blocks into ranges of at most `cap` rows, pass 2 compacts range after range into one of two
-// staging buffers (device + pinned) while the host takes the previous range's rows.  Device memory: 2 x cap x 12 bytes
-// + 4 bytes per block, whatever the table holds (cap: 2^22 rows, BC_FINISH_CHUNK_ROWS).
-static int finish_dense(bc_engine* e, const std::function<int(uint64_t)>& on_total,
-                        const std::function<int(const uint64_t*, const uint32_t*, uint64_t)>& on_rows, uint64_t* n_rows) {
-  if (n_rows) *n_rows = 0;
-  const uint64_t entries = e->table_entries;
-  if (entries == 0) return on_total(0);
-  uint64_t cap = 1ull << 22;
-  if (const char* ev = getenv("BC_FINISH_CHUNK_ROWS")) cap = std::max<uint64_t>(256, strtoull(ev, nullptr, 0));
-  uint64_t block = 256;
-  while (block * 2 <= cap && block < (1ull << 20)) block *= 2;
-  const uint64_t n_blocks = (entries + block - 1) / block;
-  const uint32_t* bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
-  ScratchGuard g;
-  uint32_t* d_per_block = nullptr;
-  HIP_TRY(g.dmalloc(&d_per_block, n_blocks * 4));
-  hipLaunchKernelGGL(count_blocks_kernel, dim3((uint32_t)std::min<uint64_t>(n_blocks, 256ull * 8)), dim3(256), 0, e->stream,
-                     e->d_table, bits, entries, block, n_blocks, d_per_block);
-  HIP_TRY(hipGetLastError());
-  std::vector<uint32_t> per_block;
-  try {
-    per_block.resize(n_blocks);
-  } catch (const std::bad_alloc&) {
-    set_error("bc_engine_finish: out of host memory");
-    return BC_ERR_NOMEM;
-  }
-  HIP_TRY(hipMemcpyAsync(per_block.data(), d_per_block, n_blocks * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  uint64_t total = 0;
-  for (uint32_t c : per_block) total += c;
-  int rc = on_total(total);
-  if (rc != BC_OK) return rc;
-  if (n_rows) *n_rows = total;
-  if (total == 0) return BC_OK;
-
-  const uint64_t slot_rows = std::min(cap, total);
-  uint64_t* d_idx[2] = {nullptr, nullptr};
-  uint32_t* d_cnt[2] = {nullptr, nullptr};
-  uint64_t* h_idx[2] = {nullptr, nullptr};
-  uint32_t* h_cnt[2] = {nullptr, nullptr};
-  hipEvent_t landed[2] = {nullptr, nullptr};
-  unsigned long long* d_cursor = nullptr;
-  HIP_TRY(g.dmalloc(&d_cursor, 16));
-  for (int k = 0; k < 2; ++k) {
-    HIP_TRY(g.dmalloc(&d_idx[k], slot_rows * 8));
-    HIP_TRY(g.dmalloc(&d_cnt[k], slot_rows * 4));
-    HIP_TRY(g.hmalloc(&h_idx[k], slot_rows * 8));
-    HIP_TRY(g.hmalloc(&h_cnt[k], slot_rows * 4));
-    HIP_TRY(g.event(&landed[k]));
-    if (total <= cap) break;  // one range: one slot
-  }
-  uint64_t pending_rows[2] = {0, 0};
-  auto consume = [&](int k) -> int {
-    HIP_TRY(hipEventSynchronize(landed[k]));
-    return pending_rows[k] ? on_rows(h_idx[k], h_cnt[k], pending_rows[k]) : BC_OK;
-  };
-  uint64_t b0 = 0;
-  int64_t seg = 0;
-  while (b0 < n_blocks) {
-    // the longest run of blocks from b0 on whose rows fit one slot (a single block always does: block <= cap)
-    uint64_t rows = 0, b1 = b0;
-    while (b1 < n_blocks && rows + per_block[b1] <= slot_rows) rows += per_block[b1++];
-    const int k = (int)(seg & 1);
-    if (rows) {
-      const uint64_t lo = b0 * block, hi = std::min(entries, b1 * block);
-      HIP_TRY(hipMemsetAsync(d_cursor + k, 0, 8, e->stream));
-      const uint32_t grid = (uint32_t)std::min<uint64_t>((hi - lo + 255) / 256, 256ull * 32);
-      hipLaunchKernelGGL(compact_range_kernel, dim3(grid), dim3(256), 0, e->stream, e->d_table, bits, lo, hi, d_cursor + k,
-                         slot_rows, d_idx[k], d_cnt[k]);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(h_idx[k], d_idx[k], rows * 8, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(h_cnt[k], d_cnt[k], rows * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    pending_rows[k] = rows;
-    HIP_TRY(hipEventRecord(landed[k], e->stream));
-    if (seg >= 1 && (rc = consume(k ^ 1)) != BC_OK) {
-      (void)hipStreamSynchronize(e->stream);  // nothing of ours may still be writing the staging buffers when they go
-      return rc;
-    }
-    b0 = b1;
-    ++seg;
-  }
-  rc = consume((int)((seg - 1) & 1));
-  (void)hipStreamSynchronize(e->stream);
-  return rc;
-}
-
-// how many rows bc_engine_finish would produce for a dense plan right now (pass 1 alone: one sweep of the table)
-int bc_engine_nonzero_entries(bc_engine* e, uint64_t* n) {
-  *n = 0;
-  if (e->h.plan.sparse || e->h.plan.has_random) {
-    set_error("bc_engine_nonzero_entries: only for plans that count into a dense table directly");
-    return BC_ERR_STATE;
-  }
-  int rc = bc_engine_sync(e);
-  if (rc) return rc;
-  const uint64_t entries = e->table_entries, block = 1ull << 20, n_blocks = (entries + block - 1) / block;
-  if (!entries) return BC_OK;
-  ScratchGuard g;
-  uint32_t* d_per_block = nullptr;
-  HIP_TRY(g.dmalloc(&d_per_block, n_blocks * 4));
-  hipLaunchKernelGGL(count_blocks_kernel, dim3((uint32_t)std::min<uint64_t>(n_blocks, 256ull * 8)), dim3(256), 0, e->stream,
-                     e->d_table, e->bits_dirty ? e->d_bits : nullptr, entries, block, n_blocks, d_per_block);
-  HIP_TRY(hipGetLastError());
-  std::vector<uint32_t> per_block(n_blocks);
-  HIP_TRY(hipMemcpyAsync(per_block.data(), d_per_block, n_blocks * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (uint32_t c : per_block) *n += c;
-  return BC_OK;
-}
-
-}  // extern "C"
-
-int bc::dense_counts_ready(bc_engine* e) {
-  int rc = bc_engine_sync(e);
-  if (rc) return rc;
-  if (e->h.plan.has_random && !e->table_materialized) return bc_engine_materialize_table(e);
-  return BC_OK;
-}
-
-extern "C" {
-
-// rows of either kind of plan, chunk by chunk (bc_engine_finish_stream); for sparse plans the chunks are cut from the
-// exported map
-static int finish_any(bc_engine* e, const std::function<int(uint64_t)>& on_total,
-                      const std::function<int(const uint64_t*, const uint32_t*, uint64_t)>& on_rows, uint64_t* n_rows) {
-  int rc;
-  if (e->h.plan.sparse) {
-    if ((rc = bc_engine_sync(e)) != BC_OK) return rc;
-    uint64_t n = 0;
-    if ((rc = finish_sparse(e, &n)) != BC_OK) return rc;
-    if (n_rows) *n_rows = n;
-    return BC_OK;  // (finish_sparse leaves the rows in e->row_idx / row_cnt; the callers below hand them on)
-  }
-  if ((rc = dense_counts_ready(e)) != BC_OK) return rc;
-  return finish_dense(e, on_total, on_rows, n_rows);
-}
-
-int bc_engine_finish(bc_engine* e, uint64_t* n_rows) {
-  if (n_rows) *n_rows = 0;
-  e->row_idx.clear();
-  e->row_cnt.clear();
-  uint64_t at = 0;
-  auto on_total = [&](uint64_t total) -> int {
-    try {
-      e->row_idx.resize(total);
-      e->row_cnt.resize(total);
-    } catch (const std::bad_alloc&) {
-      e->row_idx = std::vector<uint64_t>();
-      e->row_cnt = std::vector<uint32_t>();
-      set_error("bc_engine_finish: out of host memory for " + std::to_string(total) +
-                " rows (bc_engine_finish_stream hands the rows over in chunks instead)");
-      return BC_ERR_NOMEM;
-    }
-    return BC_OK;
-  };
-  auto on_rows = [&](const uint64_t* idx, const uint32_t* cnt, uint64_t n) -> int {
-    staged_copy(e->row_idx.data() + at, idx, n * 8);
-    staged_copy(e->row_cnt.data() + at, cnt, n * 4);
-    at += n;
-    return BC_OK;
-  };
-  const int rc = finish_any(e, on_total, on_rows, n_rows);
-  if (rc != BC_OK) {
-    e->row_idx.clear();
-    e->row_cnt.clear();
-    if (n_rows) *n_rows = 0;
-  }
-  return rc;
-}
-
-int bc_engine_finish_stream(bc_engine* e, bc_rows_fn fn, void* user, uint64_t* n_rows) {
-  if (!fn) {
-    set_error("bc_engine_finish_stream: null callback");
-    return BC_ERR_INVALID;
-  }
-  if (n_rows) *n_rows = 0;
-  e->row_idx.clear();
-  e->row_cnt.clear();
-  auto on_total = [&](uint64_t) -> int { return BC_OK; };
-  auto on_rows = [&](const uint64_t* idx, const uint32_t* cnt, uint64_t n) -> int {
-    if (fn(idx, cnt, n, user) != 0) {
-      set_error("bc_engine_finish_stream: stopped by the callback");
-      return BC_ERR_STATE;
-    }
-    return BC_OK;
-  };
-  uint64_t n = 0;
-  int rc = finish_any(e, on_total, on_rows, &n);
-  if (rc != BC_OK) return rc;
-  if (e->h.plan.sparse && e->key_words > 1) {
-    e->row_wide.clear();
-    e->row_cnt.clear();
-    set_error("bc_engine_finish_stream: the plan's keys are " + std::to_string(e->key_words) +
-              " words wide; read its rows with bc_engine_finish + bc_engine_row_text");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->h.plan.sparse) {
-    // a key map's rows are already on the host (finish_sparse): hand them on in slices, then drop them
-    const uint64_t slice = 1ull << 20;
-    for (uint64_t a = 0; a < n && rc == BC_OK; a += slice)
-      rc = on_rows(e->row_idx.data() + a, e->row_cnt.data() + a, std::min(slice, n - a));
-    e->row_idx.clear();
-    e->row_cnt.clear();
-  }
-  if (rc == BC_OK && n_rows) *n_rows = n;
-  return rc;
-}
-
-int bc_engine_decode_index(const bc_engine* e, uint64_t dense_index, uint32_t* sample_idx, uint32_t* barcode_idx) {
-  const DevPlan& P = e->h.plan;
-  if (P.sparse) {
-    set_error("bc_engine_decode_index: the plan keeps raw captures, whose keys are not indices");
-    return BC_ERR_STATE;
-  }
-  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
-  uint64_t di = dense_index;
-  for (int b = (int)e->barcode_num - 1; b >= 0; --b) {
-    const uint32_t nr = P.groups[g0 + b].n_refs;
-    if (barcode_idx) barcode_idx[b] = (uint32_t)(di % nr);
-    di /= nr;
-  }
-  if (sample_idx) *sample_idx = (uint32_t)di;
-  return BC_OK;
-}
-
-}  // extern "C"
-
-bool bc::enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples) {
-  const DevPlan& P = e->h.plan;
-  if (P.sparse) {
-    set_error(std::string(who) + ": the plan keeps raw captures, whose keys are sequences, not indices: enrich its rows "
-              "(bc_engine_row_text) on the host");
-    return false;
-  }
-  if (e->barcode_num > (uint32_t)kEnrichMaxG) {  // (cannot happen: a plan has at most kMaxGroups groups)
-    set_error(std::string(who) + ": more counted barcodes than the enrichment kernel takes");
-    return false;
-  }
-  memset(sh, 0, sizeof(*sh));
-  sh->G = e->barcode_num;
-  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
-  sh->inner = 1;
-  for (uint32_t g = 0; g < sh->G; ++g) {
-    sh->n[g] = P.groups[g0 + g].n_refs;
-    sh->single_off[g] = sh->sum_n;
-    sh->sum_n += sh->n[g];
-    sh->inner *= sh->n[g];
-  }
-  if (sh->G >= 3)  // (the reference writes Double files only then, output.rs:176, 349)
-    for (uint32_t g = 0; g + 1 < sh->G; ++g)
-      for (uint32_t h = g + 1; h < sh->G; ++h) {
-        sh->pair_off[enrich_pair_index((int)sh->G, (int)g, (int)h)] = sh->pairs;
-        sh->pairs += (uint64_t)sh->n[g] * sh->n[h];
-      }
-  *n_samples = sh->inner ? e->table_entries / sh->inner : 0;
-  return true;
-}
-
-extern "C" {
-
-int bc_engine_enrich_entries(const bc_engine* e, uint64_t* single_entries, uint64_t* double_entries) {
-  EnrichShape sh;
-  uint64_t S = 0;
-  if (!enrich_shape(e, "bc_engine_enrich_entries", &sh, &S)) return BC_ERR_UNSUPPORTED;
-  if (single_entries) *single_entries = S * sh.sum_n;
-  if (double_entries) *double_entries = S * sh.pairs;
-  return BC_OK;
-}
-
-// Single and pair counts as marginal sums of the dense table, in one pass over it on the device (bc_enrich.hip).  The
-// table, the bit map and the rows stay as they are.
-int bc_engine_enrich(bc_engine* e, uint64_t* single_counts, uint64_t* double_counts) {
-  EnrichShape sh;
-  uint64_t S = 0;
-  if (!enrich_shape(e, "bc_engine_enrich", &sh, &S)) return BC_ERR_UNSUPPORTED;
-  const uint64_t n_single = S * sh.sum_n, n_double = double_counts ? S * sh.pairs : 0;
-  if (n_single && !single_counts) {
-    set_error("bc_engine_enrich: single_counts is NULL");
-    return BC_ERR_INVALID;
-  }
-  int rc = dense_counts_ready(e);
-  if (rc) return rc;
-  if (n_single == 0) return BC_OK;
-  ScratchGuard g;
-  unsigned long long *d_single = nullptr, *d_double = nullptr;
-  HIP_TRY(g.dmalloc(&d_single, n_single * 8));
-  if (n_double) HIP_TRY(g.dmalloc(&d_double, n_double * 8));
-  HIP_TRY(hipMemsetAsync(d_single, 0, n_single * 8, e->stream));
-  if (n_double) HIP_TRY(hipMemsetAsync(d_double, 0, n_double * 8, e->stream));
-  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, d_single, d_double,
-                           e->stream));
-  HIP_TRY(hipMemcpyAsync(single_counts, d_single, n_single * 8, hipMemcpyDeviceToHost, e->stream));
-  if (n_double) HIP_TRY(hipMemcpyAsync(double_counts, d_double, n_double * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return BC_OK;
-}
-
-// Random-barcode plans with a dense table: the count of a tuple is the number of distinct random barcodes seen with it
-// (output.rs:265-270).  Writes those counts of the engine's CURRENT key set into its table.  bc_engine_finish does this
-// itself for a single-GPU run; a multi-GPU job calls it on every rank after the key exchange (each key then has one
-// owner), sums the tables onto the root, and the root's bc_engine_finish compacts the summed table as it stands.
-int bc_engine_materialize_table(bc_engine* e) {
-  if (!e->h.plan.has_random || e->h.plan.sparse) {
-    set_error("bc_engine_materialize_table: the plan has no random barcode with a dense table");
-    return BC_ERR_STATE;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  counts_changed(e);
-  {
-    const int rc = settle_owed(e);
-    if (rc != BC_OK) return rc;
-  }
-  HIP_TRY(hipMemsetAsync(e->d_table, 0, e->table_entries * 4, e->stream));
-  if (e->d_slots) {
-    hipLaunchKernelGGL(set_to_table_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->n_slots,
-                       e->h.plan.rspace, e->d_table);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->table_materialized = true;
-  return BC_OK;
-}
-
-int bc_engine_rows(bc_engine* e, uint64_t first, uint64_t n, uint32_t* sample_idx, uint32_t* barcode_idx,
-                   uint64_t* count) {
-  if (first + n > e->row_idx.size()) {
-    set_error("bc_engine_rows: range outside the compacted rows (call bc_engine_finish first)");
-    return BC_ERR_STATE;
-  }
-  const DevPlan& P = e->h.plan;
-  if (P.sparse) {
-    set_error("bc_engine_rows: the plan keeps raw captures, which have no index; use bc_engine_row_text");
-    return BC_ERR_STATE;
-  }
-  const uint32_t nb = e->barcode_num ? e->barcode_num : 1;
-  const uint32_t g0 = e->has_sample_group ? 1u : 0u;  // groups[0] is the sample group when present
-  for (uint64_t r = 0; r < n; ++r) {
-    uint64_t di = e->row_idx[first + r];
-    for (int b = (int)e->barcode_num - 1; b >= 0; --b) {
-      const uint32_t nr = P.groups[g0 + b].n_refs;
-      barcode_idx[r * nb + b] = (uint32_t)(di % nr);
-      di /= nr;
-    }
-    sample_idx[r] = (uint32_t)di;
-    count[r] = e->row_cnt[first + r];
-  }
-  return BC_OK;
-}
-
-int bc_engine_key_count(bc_engine* e, uint64_t* n) {
-  *n = 0;
-  if (!e->h.plan.has_random || !e->d_slots) return BC_OK;
-  return bc_engine_export_keys(e, nullptr, 0, n);
-}
-
-int bc_engine_export_keys(bc_engine* e, void* d_keys, uint64_t capacity, uint64_t* n) {
-  *n = 0;
-  if (!e->h.plan.has_random) {
-    set_error("bc_engine_export_keys: the plan has no random barcode");
-    return BC_ERR_STATE;
-  }
-  int rc = bc_engine_sync(e);
-  if (rc) return rc;
-  if (!e->d_slots) return BC_OK;
-  ScratchGuard g;
-  unsigned long long* d_n = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  if (e->key_words > 1)
-    hipLaunchKernelGGL(wide_export_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_ready,
-                       (const uint32_t*)nullptr, e->n_slots, e->key_words, d_n, (unsigned long long*)d_keys, (uint32_t*)nullptr,
-                       d_keys ? capacity : 0);
-  else
-    hipLaunchKernelGGL(set_export_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->n_slots, d_n,
-                       (unsigned long long*)d_keys, d_keys ? capacity : 0);
-  HIP_TRY(hipGetLastError());
-  unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  *n = cnt;
-  if (d_keys && cnt > capacity) {
-    set_error("bc_engine_export_keys: buffer too small");
-    return BC_ERR_INVALID;
-  }
-  return BC_OK;
-}
-
-int bc_engine_import_keys(bc_engine* e, const void* d_keys, uint64_t n, uint64_t* n_new) {
-  if (n_new) *n_new = 0;
-  if (!e->h.plan.has_random) {
-    set_error("bc_engine_import_keys: the plan has no random barcode");
-    return BC_ERR_STATE;
-  }
-  if (n == 0) return BC_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  e->table_materialized = false;
-  counts_changed(e);
-  int rc = set_reserve(e, n);
-  if (rc) return rc;
-  ScratchGuard g;
-  unsigned long long* d_n = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  if (e->key_words > 1)
-    hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, (const unsigned long long*)d_keys,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, n, e->key_words, e->d_slots, e->d_ready, (uint32_t*)nullptr,
-                       e->n_slots - 1, 0, 0u, 0u, d_n);
-  else
-    hipLaunchKernelGGL(set_insert_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, (const unsigned long long*)d_keys, n,
-                       e->d_slots, e->n_slots - 1, d_n);
-  HIP_TRY(hipGetLastError());
-  unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (n_new) *n_new = cnt;
-  return BC_OK;
-}
-
-// ---- raw-key plans without a random barcode: the counts live in a (key -> count) map -------------
-static int need_count_map(bc_engine* e, const char* who) {
-  if (!e->h.plan.sparse || e->h.plan.has_random) {
-    set_error(std::string(who) + ": the plan does not keep its counts in a key map (it has a dense table or a random barcode)");
-    return BC_ERR_STATE;
-  }
-  return BC_OK;
-}
-
-int bc_engine_export_counts(bc_engine* e, void* d_keys, void* d_counts, uint64_t capacity, uint64_t* n) {
-  *n = 0;
-  int rc = need_count_map(e, "bc_engine_export_counts");
-  if (rc) return rc;
-  if ((rc = bc_engine_sync(e))) return rc;
-  if (!e->d_slots) return BC_OK;
-  const bool write = d_keys && d_counts;
-  ScratchGuard g;
-  unsigned long long* d_n = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, e->stream));
-  if (e->key_words > 1)
-    hipLaunchKernelGGL(wide_export_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_ready, e->d_vals,
-                       e->n_slots, e->key_words, d_n, (unsigned long long*)(write ? d_keys : nullptr),
-                       (uint32_t*)(write ? d_counts : nullptr), write ? capacity : 0);
-  else
-    hipLaunchKernelGGL(map_export_checked_kernel, dim3(grid_for(e->n_slots)), dim3(256), 0, e->stream, e->d_slots, e->d_vals,
-                       e->n_slots, d_n, (unsigned long long*)d_keys, (uint32_t*)d_counts, write ? capacity : 0);
-  HIP_TRY(hipGetLastError());
-  unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, d_n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  *n = cnt;
-  if (write && cnt > capacity) {
-    set_error("bc_engine_export_counts: buffers too small");
-    return BC_ERR_INVALID;
-  }
-  return BC_OK;
-}
-
-int bc_engine_import_counts(bc_engine* e, const void* d_keys, const void* d_counts, uint64_t n) {
-  int rc = need_count_map(e, "bc_engine_import_counts");
-  if (rc) return rc;
-  if (n == 0) return BC_OK;
-  if (!d_keys || !d_counts) {
-    set_error("bc_engine_import_counts: null buffer");
-    return BC_ERR_INVALID;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  counts_changed(e);
-  if ((rc = set_reserve(e, n))) return rc;
-  if (e->key_words > 1)
-    hipLaunchKernelGGL(wide_insert_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, (const unsigned long long*)d_keys,
-                       (const uint32_t*)nullptr, (const uint32_t*)d_counts, n, e->key_words, e->d_slots, e->d_ready, e->d_vals,
-                       e->n_slots - 1, 0, 0u, 0u, (unsigned long long*)nullptr);
-  else
-    hipLaunchKernelGGL(map_add_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, (const unsigned long long*)d_keys,
-                       (const uint32_t*)d_counts, n, e->d_slots, e->d_vals, e->n_slots - 1);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return BC_OK;
-}
-
-int bc_engine_clear_keys(bc_engine* e) {
-  HIP_TRY(hipSetDevice(e->device));
-  counts_changed(e);
-  if (e->d_slots) {
-    hipLaunchKernelGGL(set_fill_kernel, dim3(grid_for(e->n_slots * e->key_words)), dim3(256), 0, e->stream, e->d_slots,
-                       e->n_slots * e->key_words);
-    HIP_TRY(hipGetLastError());
-    if (e->d_vals) HIP_TRY(hipMemsetAsync(e->d_vals, 0, e->n_slots * 4, e->stream));
-    if (e->d_ready) HIP_TRY(hipMemsetAsync(e->d_ready, 0, e->n_slots * 4, e->stream));
-  }
-  e->key_bound = 0;
-  e->table_materialized = false;
-  return BC_OK;
-}
-
-int bc_engine_row_text(bc_engine* e, uint64_t row, char* sample, size_t sample_cap, char* tuple, size_t tuple_cap,
-                       uint64_t* count) {
-  if (row >= e->row_cnt.size() || (e->key_words == 1 && row >= e->row_idx.size())) {
-    set_error("bc_engine_row_text: row outside the compacted rows (call bc_engine_finish first)");
-    return BC_ERR_STATE;
-  }
-  const DevPlan& P = e->h.plan;
-  std::string s_out = "barcode", t_out;  // parse.rs:473: the sample key without a sample group
-  std::vector<std::string> parts(P.n_groups);
-  if (e->key_words > 1) {
-    // wide key (bc_long.h): every group's field read back from the payload bits
-    const uint64_t* key = &e->row_wide[row * e->key_words];
-    auto bit = [&](uint32_t at) { return (uint32_t)((key[1u + (at >> 6)] >> (at & 63u)) & 1ull); };
-    for (uint32_t g = 0; g < P.n_groups; ++g) {
-      const LongGroup& G = e->lh.plan.groups[g];
-      if (G.n_refs) {
-        uint32_t idx = 0;
-        for (uint32_t b = 0; b < 32u; ++b) idx |= bit(G.key_bit + b) << b;
-        parts[g] = idx < e->set_seqs[g].size() ? e->set_seqs[g][idx] : std::string("?");
-      } else {
-        std::string v;
-        for (uint32_t i = 0; i < G.len; ++i) {
-          const uint32_t b1 = bit(G.key_bit + i), b2 = bit(G.key_bit + G.len + i), bn = bit(G.key_bit + 2u * G.len + i);
-          v.push_back(bn ? 'N' : "ACTG"[b1 | (b2 << 1)]);
-        }
-        parts[g] = v;
-      }
-    }
-  }
-  uint64_t key = e->key_words > 1 ? 0 : e->row_idx[row];
-  for (int g = (int)P.n_groups - 1; g >= 0 && e->key_words == 1; --g) {
-    const DevGroup& G = P.groups[g];
-    std::string v;
-    if (G.mode == kSetNone) {
-      uint64_t radix = 1;
-      for (uint32_t k = 0; k < G.len; ++k) radix *= 5;
-      uint64_t code = key % radix;
-      key /= radix;
-      for (uint32_t k = 0; k < G.len; ++k) {
-        v.push_back("ACTGN"[code % 5]);
-        code /= 5;
-      }
-    } else {
-      const uint32_t idx = (uint32_t)(key % G.n_refs);
-      key /= G.n_refs;
-      v = e->set_seqs[g][idx];
-    }
-    parts[g] = v;
-  }
-  for (uint32_t g = 0; g < P.n_groups; ++g) {
-    if (P.groups[g].type == kGroupSample)
-      s_out = parts[g];
-    else
-      t_out += (t_out.empty() ? "" : ",") + parts[g];
-  }
-  if (s_out.size() + 1 > sample_cap || t_out.size() + 1 > tuple_cap) {
-    set_error("bc_engine_row_text: buffer too small");
-    return BC_ERR_INVALID;
-  }
-  memcpy(sample, s_out.c_str(), s_out.size() + 1);
-  memcpy(tuple, t_out.c_str(), t_out.size() + 1);
-  if (count) *count = e->row_cnt[row];
-  return BC_OK;
-}
 
 int bc_engine_timing(bc_engine* e, int enable) {
   e->timing = enable != 0;
-  return BC_OK;
-}
-
-int bc_table_pack_u8(const void* d_table_u32, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64, void* d_ovf_val_u32,
-                     uint64_t ovf_capacity, uint64_t* n_ovf, int device_id, void* hip_stream) {
-  return bc_internal_table_pack_u8(d_table_u32, nullptr, n, d_out_u8, d_ovf_idx_u64, d_ovf_val_u32, ovf_capacity, n_ovf, device_id,
-                                   hip_stream);
-}
-
-// (not part of the documented ABI) the same with the first-occurrence bit map of two-level counting read alongside:
-// what travels is table + bit, without a fold pass first (bc_comm.hip)
-int bc_internal_table_pack_u8(const void* d_table_u32, const void* d_bits, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64,
-                              void* d_ovf_val_u32, uint64_t ovf_capacity, uint64_t* n_ovf, int device_id, void* hip_stream) {
-  if (n_ovf) *n_ovf = 0;
-  if (n == 0) return BC_OK;
-  if (!d_table_u32 || !d_out_u8 || ((uintptr_t)d_table_u32 & 15) || ((uintptr_t)d_out_u8 & 3)) {
-    set_error("bc_table_pack_u8: null or misaligned buffer (table 16-byte, output 4-byte aligned)");
-    return BC_ERR_INVALID;
-  }
-  HIP_TRY(hipSetDevice(device_id));
-  hipStream_t st = (hipStream_t)hip_stream;
-  ScratchGuard g;
-  unsigned long long* d_n = nullptr;
-  HIP_TRY(g.dmalloc(&d_n, 8));
-  HIP_TRY(hipMemsetAsync(d_n, 0, 8, st));
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((n / 4 + 255) / 256 + 1, 256ull * 64);
-  hipLaunchKernelGGL(table_pack_u8_kernel, dim3(grid), dim3(256), 0, st, (const uint32_t*)d_table_u32, (const uint32_t*)d_bits, n, (uint8_t*)d_out_u8, d_n,
-                     (unsigned long long*)d_ovf_idx_u64, (uint32_t*)d_ovf_val_u32, d_ovf_idx_u64 && d_ovf_val_u32 ? ovf_capacity : 0);
-  HIP_TRY(hipGetLastError());
-  unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, d_n, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (n_ovf) *n_ovf = cnt;
-  return BC_OK;
-}
-
-int bc_table_sum_u8(const void* d_rows_u8, uint32_t n_rows, uint64_t n, void* d_out_u32, int device_id, void* hip_stream) {
-  if (n == 0) return BC_OK;
-  if (!d_rows_u8 || !d_out_u32 || (n & 3) || ((uintptr_t)d_rows_u8 & 3) || ((uintptr_t)d_out_u32 & 15)) {
-    set_error("bc_table_sum_u8: null or misaligned buffer, or a slice length that is not a multiple of 4");
-    return BC_ERR_INVALID;
-  }
-  HIP_TRY(hipSetDevice(device_id));
-  hipStream_t st = (hipStream_t)hip_stream;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((n / 4 + 255) / 256, 256ull * 64);
-  hipLaunchKernelGGL(table_sum_u8_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t*)d_rows_u8, n_rows, n, (uint32_t*)d_out_u32);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  return BC_OK;
-}
-
-int bc_probe_atomic_rate(int device_id, void* d_table_u32, uint64_t entries, uint64_t n_atomics, double* atomics_per_s) {
-  *atomics_per_s = 0.0;
-  if (!d_table_u32 || entries == 0 || n_atomics == 0) {
-    set_error("bc_probe_atomic_rate: null table or nothing to do");
-    return BC_ERR_INVALID;
-  }
-  HIP_TRY(hipSetDevice(device_id));
-  const uint32_t per = 16;
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_atomics / per + 255) / 256, 1u << 20);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  HIP_TRY(hipEventRecord(e0, 0));
-  hipLaunchKernelGGL(atomic_probe_kernel, dim3(blocks), dim3(256), 0, 0, (uint32_t*)d_table_u32, entries, per, 2ull, 1u);
-  HIP_TRY(hipEventRecord(e1, 0));
-  hipLaunchKernelGGL(atomic_probe_kernel, dim3(blocks), dim3(256), 0, 0, (uint32_t*)d_table_u32, entries, per, 2ull, 0xFFFFFFFFu);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (ms > 0.f) *atomics_per_s = (double)blocks * 256.0 * per / (ms * 1e-3);
   return BC_OK;
 }
 
@@ -2322,21 +1183,6 @@ int bc_engine_gz_segments_inflated(const bc_engine* e, uint64_t* n) {
   return BC_OK;
 }
 
-int bc_engine_sclk_mhz(bc_engine* e, double* mhz) {
-  *mhz = 0.0;
-  HIP_TRY(hipSetDevice(e->device));
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 24));
-  hipLaunchKernelGGL(sclk_probe_kernel, dim3(1), dim3(64), 0, e->stream, d);
-  HIP_TRY(hipGetLastError());
-  unsigned long long h[3] = {0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipFree(d);
-  if (h[1]) *mhz = 100.0 * (double)h[0] / (double)h[1];
-  return BC_OK;
-}
-
 // resolves the recorded event pairs into per-launch times (the stream has drained)
 static int collect_launch_times(bc_engine* e) {
   int rc = bc_engine_sync(e);
@@ -2368,269 +1214,6 @@ int bc_engine_kernel_ms_each(bc_engine* e, double* ms_out, uint64_t capacity, ui
   if (rc) return rc;
   if (launches) *launches = e->launch_ms.size();
   for (uint64_t i = 0; ms_out && i < capacity && i < e->launch_ms.size(); ++i) ms_out[i] = e->launch_ms[i];
-  return BC_OK;
-}
-
-// classify one ASCII string into planes; returns false if longer than 32
-static bool pack_query(const char* s, uint32_t& q1, uint32_t& q2, uint32_t& qn, uint32_t& qx, uint32_t& len) {
-  q1 = q2 = qn = qx = 0;
-  len = (uint32_t)strlen(s);
-  if (len > 32) return false;
-  for (uint32_t i = 0; i < len; ++i) {
-    const char c = s[i];
-    if (c == 'N')
-      qn |= 1u << i;
-    else if (c == 'A' || c == 'C' || c == 'G' || c == 'T') {
-      q1 |= (uint32_t)((c >> 1) & 1) << i;
-      q2 |= (uint32_t)((c >> 2) & 1) << i;
-    } else {
-      qx |= 1u << i;
-    }
-  }
-  return true;
-}
-
-int64_t bc_fix_error(const char* mismatch_seq, const char* const* possible_seqs, uint64_t n, uint16_t mismatches,
-                     int device_id) {
-  uint32_t q1, q2, qn, qx, qlen;
-  if (!pack_query(mismatch_seq, q1, q2, qn, qx, qlen)) {
-    set_error("bc_fix_error: sequences longer than 32 bases are not supported");
-    return BC_ERR_UNSUPPORTED - 1;
-  }
-  std::vector<uint32_t> r1(n), r2(n), rn(n);
-  std::vector<uint8_t> rl(n);
-  for (uint64_t j = 0; j < n; ++j) {
-    uint32_t x, l;
-    if (!pack_query(possible_seqs[j], r1[j], r2[j], rn[j], x, l) || x) {
-      set_error("bc_fix_error: candidates must be A,C,G,T,N strings of at most 32 bases");
-      return BC_ERR_UNSUPPORTED - 1;
-    }
-    rl[j] = (uint8_t)l;
-  }
-  if (hipSetDevice(device_id) != hipSuccess) {
-    set_error("bc_fix_error: no HIP device (the engine has no CPU path)");
-    return BC_ERR_HIP - 1;
-  }
-  DevGroup G;
-  memset(&G, 0, sizeof G);
-  G.len = qlen;
-  G.n_refs = (uint32_t)n;
-  G.max_err = mismatches;
-  void *d1 = nullptr, *d2 = nullptr, *dn = nullptr, *dl = nullptr, *dout = nullptr;
-  bool ok = hipMalloc(&d1, n * 4 + 16) == hipSuccess && hipMalloc(&d2, n * 4 + 16) == hipSuccess &&
-            hipMalloc(&dn, n * 4 + 16) == hipSuccess && hipMalloc(&dl, n + 16) == hipSuccess &&
-            hipMalloc(&dout, 16) == hipSuccess;
-  uint32_t out = kFail;
-  if (ok && n) {
-    ok = hipMemcpy(d1, r1.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d2, r2.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dn, rn.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dl, rl.data(), n, hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (ok) {
-    G.r1_a = (uint64_t)(uintptr_t)d1;
-    G.r2_a = (uint64_t)(uintptr_t)d2;
-    G.rn_a = (uint64_t)(uintptr_t)dn;
-    G.rlen_a = (uint64_t)(uintptr_t)dl;
-    hipLaunchKernelGGL(fix_error_kernel, dim3(1), dim3(64), 0, 0, G, q1, q2, qn, qx, (uint32_t*)dout);
-    ok = hipGetLastError() == hipSuccess && hipMemcpy(&out, dout, 4, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  (void)hipFree(d1);
-  (void)hipFree(d2);
-  (void)hipFree(dn);
-  (void)hipFree(dl);
-  (void)hipFree(dout);
-  if (!ok) {
-    set_error(std::string("bc_fix_error: HIP failure: ") + hipGetErrorString(hipGetLastError()));
-    return BC_ERR_HIP - 1;
-  }
-  return out == kFail ? -1 : (int64_t)out;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// synthetic workloads
-// ------------------------------------------------------------------------------------------------
-struct bc_synth {
-  SynthDev S;                       // host view (refs -> host memory)
-  std::vector<std::string> flat;    // per group: concatenated reference bases
-  int dev_device = -1;
-  SynthDev D;                       // device view (refs -> device memory)
-  std::vector<void*> dev_allocs;
-};
-
-extern "C" {
-
-bc_synth* bc_synth_create(const bc_plan* p, const bc_synth_params* prm) {
-  if (!p || !prm) {
-    set_error("bc_synth_create: null argument");
-    return nullptr;
-  }
-  if (!p->unsupported.empty() || p->length > (uint32_t)kSynthMaxL || p->groups.size() > (size_t)kMaxGroups) {
-    set_error("bc_synth_create: scheme not supported by the generator");
-    return nullptr;
-  }
-  if (prm->read_len <= p->length || prm->phred_hi < prm->phred_lo || prm->lowq_hi < prm->lowq_lo) {
-    set_error("bc_synth_create: read_len must exceed the format length; Phred ranges must be ordered");
-    return nullptr;
-  }
-  bc_synth* s = new bc_synth();
-  SynthDev& S = s->S;
-  memset(&S, 0, sizeof S);
-  S.seed = prm->seed;
-  S.read_len = prm->read_len;
-  S.L = p->length;
-  S.p_sub = prm->p_sub;
-  S.p_n = prm->p_n;
-  S.p_lowq = prm->p_lowq;
-  S.phred_lo = prm->phred_lo;
-  S.phred_hi = prm->phred_hi;
-  S.lowq_lo = prm->lowq_lo;
-  S.lowq_hi = prm->lowq_hi;
-  S.n_molecules = prm->n_molecules;
-  S.zipf = prm->zipf;
-  S.geo_total = prm->geo_total;
-  S.n_groups = (uint32_t)p->groups.size();
-  s->flat.resize(S.n_groups);
-  for (uint32_t g = 0; g < S.n_groups; ++g) {
-    const auto& fg = p->groups[g];
-    SynthGroup& G = S.groups[g];
-    G.type = fg.type;
-    G.off = fg.off;
-    G.len = fg.len;
-    const KnownSet* set = nullptr;
-    if (fg.type == kGroupSample && p->samples.size()) set = &p->samples;
-    if (fg.type == kGroupBarcode && p->counted_loaded) set = &p->counted[fg.number - 1];
-    if (fg.type != kGroupRandom) S.n_sb++;
-    if (set) {
-      for (const auto& q : set->seqs) {
-        if (q.size() != fg.len) {
-          set_error("bc_synth_create: every known barcode must have the length of its group");
-          delete s;
-          return nullptr;
-        }
-        s->flat[g] += q;
-      }
-      G.n_refs = (uint32_t)set->size();
-      // a multiplier coprime to the set size: rank -> reference index is then a bijection
-      uint32_t mul = G.n_refs > 2 ? 2654435761u % G.n_refs : 1u;
-      auto gcd = [](uint32_t a, uint32_t b) {
-        while (b) {
-          const uint32_t t = a % b;
-          a = b;
-          b = t;
-        }
-        return a;
-      };
-      if (G.n_refs > 2) {
-        while (mul < 2u || gcd(mul, G.n_refs) != 1u) mul = mul + 1u >= G.n_refs ? 2u : mul + 1u;  // n - 1 is coprime to n
-      } else {
-        mul = 1u;
-      }
-      G.zmul = mul;
-    }
-  }
-  for (uint32_t g = 0; g < S.n_groups; ++g) S.groups[g].refs = s->flat[g].data();
-  for (uint32_t i = 0; i < p->pos.size(); ++i) {
-    const auto& fp = p->pos[i];
-    S.fmt[i] = fp.kind == kPosConst ? (uint8_t)fp.letter : (fp.kind == kPosFmtN ? (uint8_t)'n' : (uint8_t)(0x80 | fp.group));
-  }
-  return s;
-}
-
-void bc_synth_destroy(bc_synth* s) {
-  if (!s) return;
-  if (s->dev_device >= 0) {
-    (void)hipSetDevice(s->dev_device);
-    for (void* p : s->dev_allocs) (void)hipFree(p);
-  }
-  delete s;
-}
-
-int bc_synth_generate_host(bc_synth* s, uint64_t first, uint64_t n, void* seq, void* qual, uint32_t stride) {
-  if (stride < s->S.read_len) {
-    set_error("bc_synth_generate: stride below read_len");
-    return BC_ERR_INVALID;
-  }
-  uint8_t* so = (uint8_t*)seq;
-  uint8_t* qo = (uint8_t*)qual;
-  for (uint64_t t = 0; t < n; ++t) {
-    SynthRead R;
-    synth_begin(s->S, first + t, R);
-    for (uint32_t p = 0; p < s->S.read_len; ++p) {
-      uint8_t b, q;
-      synth_byte(s->S, first + t, R, p, b, q);
-      so[t * stride + p] = b;
-      if (qo) qo[t * stride + p] = q;
-    }
-    for (uint32_t p = s->S.read_len; p < stride; ++p) {
-      so[t * stride + p] = '\n';
-      if (qo) qo[t * stride + p] = '\n';
-    }
-  }
-  return BC_OK;
-}
-
-int bc_synth_generate_device(bc_synth* s, int device_id, void* hip_stream, uint64_t first, uint64_t n, void* d_seq,
-                             void* d_qual, uint32_t stride) {
-  if (stride < s->S.read_len) {
-    set_error("bc_synth_generate: stride below read_len");
-    return BC_ERR_INVALID;
-  }
-  HIP_TRY(hipSetDevice(device_id));
-  if (s->dev_device != device_id) {
-    for (void* p : s->dev_allocs) (void)hipFree(p);
-    s->dev_allocs.clear();
-    s->D = s->S;
-    for (uint32_t g = 0; g < s->S.n_groups; ++g) {
-      void* d = nullptr;
-      HIP_TRY(hipMalloc(&d, s->flat[g].size() + 16));
-      s->dev_allocs.push_back(d);
-      if (!s->flat[g].empty()) HIP_TRY(hipMemcpy(d, s->flat[g].data(), s->flat[g].size(), hipMemcpyHostToDevice));
-      s->D.groups[g].refs = (const char*)d;
-    }
-    s->dev_device = device_id;
-  }
-  if (n == 0) return BC_OK;
-  const uint64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(synth_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)hip_stream, s->D, first, n,
-                     (uint8_t*)d_seq, (uint8_t*)d_qual, stride);
-  HIP_TRY(hipGetLastError());
-  return BC_OK;
-}
-
-int bc_synth_make_set(uint64_t seed, uint32_t n, uint32_t k, uint32_t min_dist, char* out) {
-  if (k == 0 || k > 32 || (k < 16 && (uint64_t)n > (1ull << (2 * k)))) {
-    set_error("bc_synth_make_set: cannot draw that many distinct k-mers");
-    return BC_ERR_INVALID;
-  }
-  std::vector<uint64_t> acc;  // 2 bits per base
-  acc.reserve(n);
-  const uint64_t mask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
-  uint64_t ctr = 0;
-  while (acc.size() < n) {
-    if (ctr > 400ull * n + 100000) {
-      set_error("bc_synth_make_set: could not place the requested k-mers at that minimum distance");
-      return BC_ERR_INVALID;
-    }
-    const uint64_t c = synth_mix(seed ^ 0xB0C0DEull, ctr++, k) & mask;
-    bool ok = true;
-    for (uint64_t a : acc) {
-      const uint64_t x = a ^ c;
-      const uint64_t diff = (x | (x >> 1)) & 0x5555555555555555ull;
-      if ((uint32_t)__builtin_popcountll(diff) < std::max(min_dist, 1u)) {
-        ok = false;
-        break;
-      }
-    }
-    if (ok) acc.push_back(c);
-  }
-  const char* acgt = "ACGT";
-  for (uint32_t i = 0; i < n; ++i) {
-    for (uint32_t b = 0; b < k; ++b) out[(size_t)i * (k + 1) + b] = acgt[(acc[i] >> (2 * b)) & 3];
-    out[(size_t)i * (k + 1) + k] = 0;
-  }
   return BC_OK;
 }
 

@@ -1,6 +1,8 @@
-// bc_engine_impl.h -- what the engine's translation units (bc_engine.hip, bc_text.hip) share: struct bc_engine, the
-// HIP_TRY / ScratchGuard pair every function of the C ABI is written with, and the few engine functions the text
-// renderers call.  Internal: no other file includes it.
+// bc_engine_impl.h -- what the engine's translation units (bc_engine.hip, bc_keys.hip, bc_finish.hip, bc_probe.hip,
+// bc_synth.hip, bc_text.hip) share: struct bc_engine, the HIP_TRY / ScratchGuard pair every function of the C ABI is
+// written with, the functions one of them defines and another calls, and the undocumented hooks of the exchange
+// (bc_comm.hip includes it for those alone).  A kernel is launched only from the file that defines it: what crosses a
+// file is a host function declared here.  Internal: no other file includes it.
 #ifndef BC_ENGINE_IMPL_H
 #define BC_ENGINE_IMPL_H
 
@@ -208,17 +210,28 @@ struct bc_engine {
 
 namespace bc {
 
-// (defined in bc_engine.hip)
+// whatever bc_engine_finish would hand out may have changed (bc_engine::counts_epoch)
+inline void counts_changed(bc_engine* e) { ++e->counts_epoch; }
+
+// ---- defined in bc_engine.hip ----
 uint32_t grid_for(uint64_t n);  // workgroups of 256 for a grid-stride loop over n items
 // src -> a device allocation the engine owns until it is freed; *out: its address
 int upload(bc_engine* e, const void* src, size_t bytes, uint64_t* out);
-// What every reader of a dense plan's counts does first (bc_engine_finish, bc_engine_enrich, the renderers): wait for the
-// submits, and for a random-barcode plan turn the key set into per-tuple counts unless that has been done for the
-// current keys.  Afterwards entry i counts table[i] + bit i of the bit map (when e->bits_dirty: two-level counting, not
-// folded).
-int dense_counts_ready(bc_engine* e);
-// The shape of a dense plan's enrichment (bc_engine_enrich); false + set_error() for plans that have none.
-bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples);
+// Everything a reset owes (bc_engine::owed_*), on the engine's stream: first thing in every path that reads or writes
+// table, dirty map or bit map.
+int settle_owed(bc_engine* e);
+// bc_fix_error's kernel: one wavefront on the null stream of the current device, *d_out its verdict; the caller reads
+// hipGetLastError()
+void fix_error_launch(const DevGroup& G, uint32_t q1, uint32_t q2, uint32_t qn, uint32_t qx, uint32_t* d_out);
+// staging copy pageable <-> pinned, cut into slices for a few threads (BC_STAGE_THREADS)
+void staged_copy(void* dst, const void* src, size_t n);
+
+// ---- defined in bc_keys.hip ----
+// Keeps the key table at most half full for `more` further keys (plans with a random barcode or raw captures; a no-op
+// for the others).  Growing allocates a table of twice the size (or more) and re-inserts the old keys on the device.
+int set_reserve(bc_engine* e, uint64_t more);
+// Empties the key table where it stands (enqueued on the engine's stream) and forgets what was derived from its keys.
+int clear_key_table(bc_engine* e);
 // The (tuple key, count) pairs of a narrow-key map as they stand, into buffers that `g` owns: a random-barcode plan's key
 // set first aggregated into per-tuple distinct counts.  e->d_slots is not NULL; the stream has drained on return.
 int export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** d_key, uint32_t** d_cnt, uint64_t* n);
@@ -227,6 +240,26 @@ int export_pairs(bc_engine* e, const char* who, ScratchGuard& g, uint64_t** d_ke
 // sorts.  e->d_slots is not NULL; the stream has drained on return.
 int export_wide(bc_engine* e, const char* who, ScratchGuard& g, unsigned long long** d_key, uint32_t** d_cnt, uint64_t* n);
 
+// ---- defined in bc_finish.hip ----
+// What every reader of a dense plan's counts does first (bc_engine_finish, bc_engine_enrich, the renderers): wait for the
+// submits, and for a random-barcode plan turn the key set into per-tuple counts unless that has been done for the
+// current keys.  Afterwards entry i counts table[i] + bit i of the bit map (when e->bits_dirty: two-level counting, not
+// folded).
+int dense_counts_ready(bc_engine* e);
+// The shape of a dense plan's enrichment (bc_engine_enrich); false + set_error() for plans that have none.
+bool enrich_shape(const bc_engine* e, const char* who, EnrichShape* sh, uint64_t* n_samples);
+
 }  // namespace bc
+
+// Hooks for the engine library's own end-of-run exchange (bc_comm.hip); not part of the documented ABI.
+extern "C" {
+// (bc_engine.hip) the table as it stands, with the bit map beside it (*bits: NULL when nothing is pending there) ...
+void* bc_internal_table_unfolded(bc_engine* e, const void** bits);
+// ... and the caller's word that the table has been overwritten with plain counts
+int bc_internal_table_now_plain(bc_engine* e);
+// (bc_probe.hip) bc_table_pack_u8 with the first-occurrence bit map of two-level counting read alongside
+int bc_internal_table_pack_u8(const void* d_table_u32, const void* d_bits, uint64_t n, void* d_out_u8, void* d_ovf_idx_u64,
+                              void* d_ovf_val_u32, uint64_t ovf_capacity, uint64_t* n_ovf, int device_id, void* hip_stream);
+}
 
 #endif

@@ -1,5 +1,5 @@
 // bc_enrich.h -- single and double barcode enrichment (bc_engine_enrich, ResultsEnrichment of info.rs:811-904) as
-// marginal sums of the dense (sample, barcode tuple) table: the launcher bc_engine.hip calls, the kernel is
+// marginal sums of the dense (sample, barcode tuple) table: the launcher bc_finish.hip calls, the kernel is
 // bc_enrich.hip.
 #ifndef BC_ENRICH_H
 #define BC_ENRICH_H
