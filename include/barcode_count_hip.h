@@ -495,7 +495,8 @@ int64_t bc_fix_error(const char *mismatch_seq, const char *const *possible_seqs,
 
 /* ---- FASTQ ingest (replaces input::read_fastq, input.rs:24-149) --------------- */
 
-/* Reads a whole *.fastq / *.fastq.gz file, frames it into 4-line records exactly as
+/* (A *.bam file is accepted as well: see "unaligned BAM" below.)
+ * Reads a whole *.fastq / *.fastq.gz file, frames it into 4-line records exactly as
  * FastqLineReader does (input.rs:115-148), and submits the sequence / quality lines to the engine in
  * batches through bc_engine_submit_host (pinned buffers, copies overlapped with the kernel).
  * *total_reads receives the reference's "Total sequences" value, including its quirks: a trailing
@@ -607,6 +608,52 @@ int bc_gunzip_span_device(int device_id, void *hip_stream, const void *d_src, ui
                           bc_gunzip_result *result);
 /* segments inflated that way for this engine since it was created (by bc_fastq_count*) */
 int bc_engine_gz_segments_inflated(const bc_engine *e, uint64_t *n);
+
+/* ---- unaligned BAM: BGZF blocks inflated and BAM records framed on the device -------------------- */
+
+/* bc_fastq_count* accept a *.bam file and count it as they would count the plain FASTQ file that `samtools fastq` with
+ * default options writes for it: the packed sequence through "=ACMGRSVTWYHKDBN", each quality byte q as
+ * min(q, 93) + 33 (a record without qualities, first byte 0xFF: all '"'), an empty sequence and quality line for
+ * l_seq == 0; a record flagged 0x10 is handed on reverse-complemented with its qualities reversed; records flagged
+ * 0x100 or 0x800 (secondary, supplementary) are skipped and not counted.  Every other record is one read, and
+ * *total_reads is their number: none of the .gz quirks apply.  Names, CIGAR, aux fields and the header are skipped.
+ * The file always goes the device way (BC_GZ_DEVICE is about .gz names; BC_INGEST_VERBOSE names the path
+ * bam-device): the BGZF blocks are inflated as above, and the records -- binary, length-prefixed, so that a record's
+ * start is known only from the record before it -- are found in parallel: every offset that could start a record by
+ * its fixed 36 bytes is a candidate, every candidate knows its successor, and jump pointers mark the one chain that
+ * starts at the first unframed byte.  BC_ERR_INVALID: not BGZF, bad magic, a header that runs past the file, a damaged
+ * block, a record chain that breaks (what follows a record is no record header, or bytes are left after the last whole
+ * record).  BC_ERR_UNSUPPORTED: l_seq above 65535, a record longer than 4 MiB.
+ * Several shards: shard 0 reads the whole file, the others nothing, as with an ordinary gzip stream.  Record-aligned
+ * BAM shards are not built. */
+
+/* The header of a BAM file (host only, no GPU): *n_ref the number of reference sequences in its dictionary,
+ * *first_record_offset where, in the inflated stream, the first record starts, *inflated_bytes the stream's length.
+ * BC_ERR_INVALID: unreadable, not BGZF, bad magic, or a header that runs past the end of the file. */
+int bc_bam_scan(const char *path, uint32_t *n_ref, uint64_t *first_record_offset, uint64_t *inflated_bytes);
+
+#define BC_BAM_OK 0
+#define BC_BAM_BROKEN_CHAIN 1  /* what follows a whole record of the chain (or lies at `start`) is no record header */
+#define BC_BAM_CAPACITY 2      /* more candidates than `capacity`: nothing is framed */
+#define BC_BAM_TOO_LONG 3      /* as BROKEN_CHAIN, but the header there would do were its record not above 4 MiB */
+
+typedef struct bc_bam_frame_result {
+  uint32_t status;        /* BC_BAM_* */
+  uint32_t reserved;
+  uint64_t n_records;     /* whole records of the chain from `start`, written to the three arrays in order */
+  uint64_t n_candidates;  /* offsets in [start, len - 36] that pass the header filter */
+  uint64_t end_pos;       /* just past the chain's last whole record (`start` when there is none) */
+} bc_bam_frame_result;
+
+/* The record framing on its own: d_text[0, len) (device memory, 16-byte aligned, under 2 GiB) holds BAM records, the
+ * first of them at `start`; n_ref is the dictionary's size.  d_rec_at / d_rec_len / d_rec_flag (device memory,
+ * `capacity` words each) receive every whole record's offset, l_seq and flag -- secondary and supplementary ones too.
+ * The chain ends where fewer than 36 bytes follow a record or a record runs past len.  Never reads outside the text,
+ * whatever it holds.  Runs on hip_stream (NULL: the default stream) and waits for it.  BC_OK whatever the text is like
+ * (the result says). */
+int bc_bam_frame_device(int device_id, void *hip_stream, const void *d_text, uint64_t len, uint64_t start, uint32_t n_ref,
+                        uint32_t *d_rec_at, uint32_t *d_rec_len, uint32_t *d_rec_flag, uint64_t capacity,
+                        bc_bam_frame_result *result);
 
 /* ---- synthetic workloads (bench + full-size parity) -------------------------------------- */
 

@@ -165,7 +165,8 @@ class Engine:
 
     def count_fastq(self, path, shard=0, n_shards=1):
         """input::read_fastq + the workers (input.rs:24-89, parse.rs:53-76): reads a .fastq / .fastq.gz
-        file and counts it; returns the reference's "Total sequences" value"""
+        file and counts it; returns the reference's "Total sequences" value.  A .bam file (unaligned BAM) is counted as
+        the FASTQ text `samtools fastq` writes for it; its total is the number of records handed on."""
         n = C.c_uint64()
         if n_shards == 1:
             _check(self._lib, self._lib.bc_fastq_count(self._e, str(path).encode(), C.byref(n), None, None))
@@ -606,6 +607,15 @@ class Synth:
     def generate_device(self, device, stream, first, n, d_seq, d_qual, stride=None):
         stride = stride or self.params.read_len
         _check(self._lib, self._lib.bc_synth_generate_device(self._s, device, stream, first, n, d_seq, d_qual, stride))
+
+
+def bam_scan(path, lib=None):
+    """the header of a BAM file, on the host: (references in its dictionary, inflated offset of the first record,
+    inflated bytes)"""
+    lib = lib or _lib.load()
+    n_ref, first, size = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    _check(lib, lib.bc_bam_scan(str(path).encode(), C.byref(n_ref), C.byref(first), C.byref(size)))
+    return n_ref.value, first.value, size.value
 
 
 def make_set(seed, n, k, min_dist=1, lib=None):

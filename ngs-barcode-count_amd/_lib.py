@@ -34,6 +34,12 @@ class GunzipResult(C.Structure):  # bc_gunzip_result
                 ("member_end", C.c_uint32), ("segments", C.c_uint32), ("rejected", C.c_uint32), ("crc32", C.c_uint32)]
 
 
+class BamFrameResult(C.Structure):  # bc_bam_frame_result
+    _fields_ = [("status", C.c_uint32), ("reserved", C.c_uint32), ("n_records", C.c_uint64), ("n_candidates", C.c_uint64),
+                ("end_pos", C.c_uint64)]
+
+
+BC_BAM_OK, BC_BAM_BROKEN_CHAIN, BC_BAM_CAPACITY, BC_BAM_TOO_LONG = 0, 1, 2, 3
 BC_GUNZIP_OK, BC_GUNZIP_OUTPUT_FULL, BC_GUNZIP_BAD_STREAM = 0, 1, 2
 INFLATE_STATUS = ["ok", "bad block type", "bad code lengths", "invalid symbol or distance", "input overrun",
                   "output overrun", "ISIZE mismatch", "CRC32 mismatch"]
@@ -157,6 +163,8 @@ ENGINE_API = {
     "bc_engine_gz_blocks_inflated": (_int, [_vp, C.POINTER(C.c_uint64)]),
     "bc_gunzip_span_device": (_int, [_int, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u32, C.POINTER(GunzipResult)]),
     "bc_engine_gz_segments_inflated": (_int, [_vp, C.POINTER(C.c_uint64)]),
+    "bc_bam_scan": (_int, [_cp, C.POINTER(_u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bc_bam_frame_device": (_int, [_int, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _u64, C.POINTER(BamFrameResult)]),
     "bc_comm_sum_u64": (_int, [_vp, C.POINTER(C.c_uint64), _int, _int]),
     "bc_synth_create": (_vp, [_vp, C.POINTER(SynthParams)]),
     "bc_synth_destroy": (None, [_vp]),

@@ -1,4 +1,5 @@
-// bc_bgzf.hpp -- BGZF block index and the launch of the device inflater, shared by bc_inflate.hip and bc_ingest.hip.
+// bc_bgzf.hpp -- BGZF block index and the launch of the device inflater, shared by bc_inflate.hip and bc_ingest.hip;
+// and what bc_bam.hip offers the ingest: the BAM header on the host, the record framing and the gather on the device.
 #pragma once
 #include <stdint.h>
 
@@ -54,5 +55,49 @@ int gunzip_span(int device_id, void* hip_stream, const void* d_src, uint64_t src
                 uint32_t history_bytes, void* d_text, uint64_t text_capacity, uint32_t part_bytes, bc_gunzip_result* res);
 // segments of ordinary gzip streams inflated on the device for this engine (bc_engine.hip)
 void engine_add_gz_segments(bc_engine* e, uint64_t n);
+
+// ---- BAM: the framing kernels of bc_bam.hip, for the ingest ----
+
+// what the device reports per framed text
+struct BamStats {
+  unsigned long long n_cand;   // offsets that pass the header filter
+  unsigned long long n_rec;    // records handed on
+  unsigned long long end_pos;  // just past the chain's last whole record (= start when there is none)
+  long long start;             // offset of the chain's first record; < 0: the overlap was too short
+  unsigned int min_len, max_len;  // l_seq over the records handed on
+  unsigned int status;         // kBam* of bc_bam.h
+  unsigned int pad;
+};
+// where the record table goes: the three arrays of bc_bam_frame_device, or the ingest's four (each set may be null)
+struct BamTables {
+  uint32_t *rec_at, *rec_len, *rec_flag;
+  uint32_t *seq_at, *qual_at;  // seq_at: bit 31 is the record's reverse-strand flag
+  uint16_t *lens, *qlens;
+};
+// the device buffers a framing works in
+struct BamWork {
+  uint32_t* cand;      // cap words: candidate offsets
+  uint32_t* link;      // cap words
+  uint32_t* mark;      // cap words
+  uint32_t* jump;      // levels * cap words
+  uint32_t* blk_cnt;   // bam_count_blocks(len, cap) words each
+  uint32_t* blk_off;
+  uint32_t cap, levels;
+};
+uint32_t bam_levels(uint32_t cap);  // jump-pointer levels that any chain among `cap` candidates needs
+size_t bam_count_blocks(uint64_t len_max, uint32_t cap);
+// Enqueues the framing of text[0, len) (16-byte aligned) on `stream`.  The chain starts at *d_next_off - buf_file_off,
+// or at `start` when d_next_off is null.  Records with one of the `skip_flags` set are left out.  Returns a hipError_t
+// as int.
+int bam_frame_launch(void* stream, const uint8_t* d_text, uint64_t len, uint32_t n_ref, const unsigned long long* d_next_off,
+                     unsigned long long buf_file_off, long long start, uint32_t skip_flags, const BamWork& work, const BamTables& out,
+                     BamStats* d_stats);
+// records [first, first + n) of the ingest's table -> the fixed-stride batch
+int bam_gather_launch(void* stream, const uint8_t* d_text, const uint32_t* d_seq_at, const uint32_t* d_qual_at, const uint16_t* d_lens,
+                      uint64_t first, uint64_t n, uint32_t stride, uint8_t* d_out_seq, uint8_t* d_out_qual);
+// The header of a BAM file through zlib on the host: how many references its dictionary has and where, in the
+// inflated stream, the first record starts.  false: *why says what is wrong with it.
+bool bam_header(int fd, const std::vector<BgzfMember>& members, uint64_t inflated, uint32_t* n_ref, uint64_t* first_record,
+                std::string* why);
 
 }  // namespace bc

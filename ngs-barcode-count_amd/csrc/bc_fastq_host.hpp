@@ -1,6 +1,6 @@
 // bc_fastq_host.hpp -- the parts of the FASTQ ingest (bc_ingest.hip) that decide counts and need no GPU: which input
 // path a file takes, the first-record check, the end-of-stream rules, the gzip member header, how a BGZF index is cut
-// into chunks and shards, and where a shard's first record starts.  Plain C++17: every function returns a code or a small
+// into chunks and shards, where a shard's first record starts, and the header of a BAM file.  Plain C++17: every function returns a code or a small
 // struct, the caller words the error.  Tested on the host with sanitizers (tests/ingest/ingest_host.cpp).
 #pragma once
 #include <stdint.h>
@@ -22,18 +22,23 @@ enum class InputPath {
   Zlib,        // *.fastq.gz through gzread on the host
   BgzfDevice,  // *.fastq.gz that is BGZF through and through: the compressed blocks travel, bc_inflate.hip inflates them
   GzipDevice,  // *.fastq.gz, any gzip stream, BC_GZ_DEVICE=all: span by span through bc_gunzip.hip
+  BamDevice,   // *.bam (unaligned BAM): BGZF blocks as above, then the record framing of bc_bam.hip instead of newlines
 };
 // The reference reads a .gz file with read_line, a plain one with BufReader::lines(): a '\r' before the newline stays
 // (input.rs:66-68 against input.rs:44), and the reader is handed one more, empty line at the end of the stream
 // (input.rs:69-73).
-inline bool gz_line_rules(InputPath p) { return p != InputPath::Plain; }
+// (Neither applies to BAM: its records are binary, and every whole one is one read.)
+inline bool gz_line_rules(InputPath p) { return p != InputPath::Plain && p != InputPath::BamDevice; }
+// the file is read by its BGZF index, block by block, and inflated by bc_inflate.hip
+inline bool bgzf_blocks(InputPath p) { return p == InputPath::BgzfDevice || p == InputPath::BamDevice; }
 // the text arrives on the device without a host copy: the host sees compressed bytes only
-inline bool text_on_device(InputPath p) { return p == InputPath::BgzfDevice || p == InputPath::GzipDevice; }
+inline bool text_on_device(InputPath p) { return bgzf_blocks(p) || p == InputPath::GzipDevice; }
 inline const char* input_path_name(InputPath p) {
   switch (p) {
     case InputPath::Plain: return "plain";
     case InputPath::Zlib: return "gzread";
     case InputPath::BgzfDevice: return "bgzf-device";
+    case InputPath::BamDevice: return "bam-device";
     default: return "gzip-device";
   }
 }
@@ -200,6 +205,45 @@ inline long long record_start_at_or_after(const ReadAt& read_at, unsigned long l
     if (buf.size() >= limit) return -1;
   }
   return from + buf.size() >= size ? (long long)size : -1;
+}
+
+// The header of a BAM file, read from its inflated bytes: magic, l_text, the text, n_ref and the reference entries
+// (l_name, name, l_ref each).  error: what is wrong with it (a literal), or null.
+struct BamHeader {
+  uint32_t n_ref;
+  uint64_t first_record;  // inflated offset just past the dictionary
+  const char* error;
+};
+inline BamHeader bam_parse_header(const ReadAt& read_at, uint64_t inflated) {
+  BamHeader h = {0, 0, nullptr};
+  auto fail = [&h](const char* what) {
+    h.error = what;
+    return h;
+  };
+  // four bytes at `at` as a little-endian word; false: the stream ends before them (or cannot be read)
+  auto word = [&](uint64_t at, uint32_t* v) {
+    unsigned char b[4];
+    if (at > inflated || inflated - at < 4 || read_at((char*)b, 4, at) != 4) return false;
+    *v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+    return true;
+  };
+  const char* cut = "the header runs past the end of the file (or a block of it is damaged)";
+  uint32_t magic = 0, l_text = 0, l_name = 0;
+  if (!word(0, &magic)) return fail("no room for the magic");
+  if (magic != 0x014D4142u) return fail("bad magic (not \"BAM\\1\")");
+  if (!word(4, &l_text)) return fail(cut);
+  uint64_t at = 8ull + l_text;
+  if (!word(at, &h.n_ref)) return fail(cut);
+  at += 4;
+  if (h.n_ref > 0x7FFFFFFFu) return fail("a negative number of references");
+  for (uint32_t r = 0; r < h.n_ref; ++r) {
+    if (!word(at, &l_name)) return fail(cut);
+    at += 4ull + l_name;
+    if (at > inflated || inflated - at < 4) return fail(cut);
+    at += 4;  // l_ref
+  }
+  h.first_record = at;
+  return h;
 }
 
 inline ReadAt plain_reader(int fd) {

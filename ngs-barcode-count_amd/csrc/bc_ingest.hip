@@ -19,7 +19,13 @@
 // Three slots rotate: while the device frames and counts chunk i, the team reads chunk i+1 and chunk i-1's batch may
 // still be in the match kernel.
 //
-// Which of four input paths a file takes (InputPath) is decided once per call.  A producer thread fills the slots through
+// A *.bam file (unaligned BAM) is a BGZF container of binary, length-prefixed records: it takes the BGZF way to the
+// device, and there the framing kernels of bc_bam.hip stand in for the newline scan and the gather (they find the chain
+// of records from the first unframed byte on, skip secondary and supplementary records, and unpack nibbles and Phred
+// bytes into the same batch).  Every whole record is one read; none of the .gz quirks apply.  With several shards a BAM
+// file goes to shard 0 whole and the others get nothing: record-aligned BAM shards are not built.
+//
+// Which of five input paths a file takes (InputPath) is decided once per call.  A producer thread fills the slots through
 // one of three Producers (plain / zlib reader, BGZF blocks, gzip spans on the device); the calling thread frames each
 // chunk, counts the one before it, and applies the end-of-stream rules.  What decides counts without a GPU -- the
 // first-record check, those rules, the gzip member header, the cut of a BGZF index into chunks and shards -- lives in
@@ -42,6 +48,7 @@
 #include <vector>
 
 #include "../../include/barcode_count_hip.h"
+#include "bc_bam.h"
 #include "bc_bgzf.hpp"
 #include "bc_fastq_host.hpp"
 #include "bc_ingest_kernels.h"
@@ -84,6 +91,7 @@ struct Slot {
   // BGZF chunks: `pin` holds the compressed bytes of blocks [first_blk, first_blk + nblk) of the file's index, the
   // inflate kernel writes their text behind the overlap of d_text
   uint8_t* d_comp = nullptr;
+  BamStats* d_bam_stats = nullptr;     // BAM: what the framing of bc_bam.hip reports (ingest_from_bam_kernel hands it on)
   bc_bgzf_block* blk_tab = nullptr;    // pinned host
   bc_bgzf_block* d_blk_tab = nullptr;
   uint32_t* blk_status = nullptr;      // pinned host
@@ -117,6 +125,21 @@ struct Ingest {
   std::string path;
   uint64_t blocks_inflated = 0;    // this call
   uint32_t stride = 0, ragged_stride = 0;
+  // BAM: the dictionary's size (a record's refID lies below it), the candidates one text may hold (a record has at least
+  // 37 bytes: an eighth more than the text can hold real ones), and the jump pointers, one set for all slots (a chunk's
+  // framing is over before the next one's begins: both are on `st`); some twenty levels of one word per candidate, 0.4 GB
+  // for chunks of 128 MiB
+  uint32_t n_ref = 0, bam_cap = 0, bam_levels_n = 0;
+  uint32_t* d_bam_jump = nullptr;
+
+  int alloc_bam() {
+    if (d_bam_jump) return BC_OK;
+    bam_cap = (uint32_t)((kOverlap + chunk) / 32);
+    bam_levels_n = bam_levels(bam_cap);
+    for (Slot& s : slot) HIP_TRY(hipMalloc((void**)&s.d_bam_stats, sizeof(BamStats)));
+    HIP_TRY(hipMalloc((void**)&d_bam_jump, (size_t)bam_cap * bam_levels_n * sizeof(uint32_t)));
+    return BC_OK;
+  }
 
   // the buffers only BGZF input needs, made at the first such call
   int alloc_bgzf() {
@@ -216,13 +239,14 @@ struct Ingest {
       if (s.blk_tab) (void)hipHostFree(s.blk_tab);
       if (s.blk_status) (void)hipHostFree(s.blk_status);
       void* dev[] = {s.d_stats, s.d_text, s.d_blk_cnt, s.d_blk_off, s.d_nl_pos, s.d_seq_at, s.d_qual_at, s.d_lens, s.d_qlens,
-                     s.d_out_seq, s.d_out_qual, s.d_comp, s.d_blk_tab, s.d_blk_status};
+                     s.d_out_seq, s.d_out_qual, s.d_comp, s.d_blk_tab, s.d_blk_status, s.d_bam_stats};
       for (void* p : dev)
         if (p) (void)hipFree(p);
       for (hipEvent_t ev : {s.uploaded, s.framed, s.gathered, s.consumed})
         if (ev) (void)hipEventDestroy(ev);
     }
     if (d_state) (void)hipFree(d_state);
+    if (d_bam_jump) (void)hipFree(d_bam_jump);
     if (gz_pin) (void)hipHostFree(gz_pin);
     if (d_gz_comp) (void)hipFree(d_gz_comp);
     if (st_gz) (void)hipStreamDestroy(st_gz);
@@ -235,7 +259,7 @@ struct Ingest {
     HIP_TRY(hipStreamWaitEvent(st, s.consumed, 0));  // the batch arrays of this slot may still be read by a match kernel
     if (kind == InputPath::GzipDevice) {
       // (the text and the overlap in front of it are in place: the producer put them there and waited for them)
-    } else if (kind != InputPath::BgzfDevice) {
+    } else if (!bgzf_blocks(kind)) {
       HIP_TRY(hipMemcpyAsync(s.d_text + kOverlap, s.pin, s.len, hipMemcpyHostToDevice, st));
       HIP_TRY(hipEventRecord(s.uploaded, st));
     } else {
@@ -256,6 +280,15 @@ struct Ingest {
     const unsigned long long buf_off = s.file_off - s.ov - mis;  // may wrap below zero only together with start >= mis
     const unsigned long long len = s.ov + mis + s.len;
     const uint32_t n_blk = (uint32_t)((len + kScanBlock - 1) / kScanBlock);
+    if (kind == InputPath::BamDevice) {
+      // the line-position array holds sixteen words per candidate: offsets, links and marks take three
+      const BamWork work = {s.d_nl_pos, s.d_nl_pos + bam_cap, s.d_nl_pos + 2 * (size_t)bam_cap, d_bam_jump, s.d_blk_cnt, s.d_blk_off,
+                            bam_cap, bam_levels_n};
+      const BamTables out = {nullptr, nullptr, nullptr, s.d_seq_at, s.d_qual_at, s.d_lens, s.d_qlens};
+      HIP_TRY((hipError_t)bam_frame_launch(st, text, len, n_ref, &d_state->next_off, buf_off, 0, 0x900u, work, out, s.d_bam_stats));
+      hipLaunchKernelGGL(ingest_from_bam_kernel, dim3(1), dim3(1), 0, st, s.d_bam_stats, s.d_stats);
+      return frame_end(b, text, len, buf_off);
+    }
     hipLaunchKernelGGL(ingest_begin_kernel, dim3(1), dim3(1), 0, st, d_state, buf_off, len, s.d_stats, text);
     hipLaunchKernelGGL(ingest_count_kernel, dim3(n_blk), dim3(256), 0, st, text, len, s.d_stats, s.d_blk_cnt);
     hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, st, s.d_blk_cnt, n_blk, s.d_blk_off, s.d_stats, line_cap);
@@ -265,6 +298,11 @@ struct Ingest {
     const unsigned long long rec_max = std::min<unsigned long long>(rec_cap, len / 4 + 1);
     hipLaunchKernelGGL(ingest_records_kernel, dim3((uint32_t)((rec_max + 255) / 256)), dim3(256), 0, st, text, s.d_nl_pos,
                        s.d_stats, gz_line_rules(kind) ? 0 : 1, s.d_seq_at, s.d_qual_at, s.d_lens, s.d_qlens);
+    return frame_end(b, text, len, buf_off);
+  }
+  // the framing's last steps: the device state moves on, the stats travel back
+  int frame_end(int b, const uint8_t* text, unsigned long long len, unsigned long long buf_off) {
+    Slot& s = slot[b];
     hipLaunchKernelGGL(ingest_advance_kernel, dim3(1), dim3(1), 0, st, d_state, s.d_stats, buf_off);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(s.stats, s.d_stats, sizeof(ChunkStats), hipMemcpyDeviceToHost, st));
@@ -313,13 +351,23 @@ struct Ingest {
     HIP_TRY(hipEventSynchronize(s.framed));
     const ChunkStats cs = *s.stats;
     *n_rec_out = 0;
-    if (kind == InputPath::BgzfDevice) {
+    if (bgzf_blocks(kind)) {
       const int rc = check_blocks(s);
       if (rc != BC_OK) return rc;
     }
     if (cs.start < 0) {
       set_error("a FASTQ record is longer than 4 MiB");
       return BC_ERR_INVALID;
+    }
+    if (kind == InputPath::BamDevice && cs.pad != kBamOk) {  // (the framing's status)
+      const std::string at = " (inflated offset " + std::to_string(s.file_off - s.ov + cs.end_pos - (s_text_len[b] - s.ov - s.len)) + ")";
+      if (cs.pad == kBamBroken) {
+        set_error("read error in " + path + ": the chain of BAM records breaks" + at + ": what follows a record is no record header");
+        return BC_ERR_INVALID;
+      }
+      set_error(cs.pad == kBamTooLong ? "a BAM record of " + path + " is longer than 4 MiB" + at + " (not supported by the engine)"
+                                      : "a chunk of " + path + " holds more BAM record headers, real or apparent, than the engine frames");
+      return BC_ERR_UNSUPPORTED;
     }
     if (cs.n_rec == 0) return BC_OK;
     if (cs.n_lines >= line_cap) {
@@ -341,8 +389,11 @@ struct Ingest {
     for (uint64_t first = 0; first < cs.n_rec; first += per) {
       const uint64_t n = std::min<uint64_t>(per, cs.n_rec - first);
       if (first) HIP_TRY(hipStreamWaitEvent(st, s.consumed, 0));  // the previous part's kernel still reads the arrays
-      hipLaunchKernelGGL(ingest_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, st, s_text[b], s.d_seq_at, s.d_qual_at,
-                         s.d_lens, s.d_qlens, first, n, stride, s.d_out_seq, s.d_out_qual);
+      if (kind == InputPath::BamDevice)
+        HIP_TRY((hipError_t)bam_gather_launch(st, s_text[b], s.d_seq_at, s.d_qual_at, s.d_lens, first, n, stride, s.d_out_seq, s.d_out_qual));
+      else
+        hipLaunchKernelGGL(ingest_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, st, s_text[b], s.d_seq_at, s.d_qual_at,
+                           s.d_lens, s.d_qlens, first, n, stride, s.d_out_seq, s.d_out_qual);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipEventRecord(s.gathered, st));
       HIP_TRY(hipStreamWaitEvent(engine_stream, s.gathered, 0));
@@ -779,8 +830,9 @@ struct Sizes {
 Sizes sizes_for(const Options& o, InputPath kind, unsigned long long bytes) {
   // chunk size: a multiple of 16 (the device reads the text 16 bytes at a time), no larger than the file needs;
   // BC_INGEST_CHUNK is for tests, which want records to straddle chunks in small files
-  size_t chunk = kind == InputPath::Plain || kind == InputPath::BgzfDevice ? (size_t)std::min<unsigned long long>(128u << 20, ((bytes >> 20) + 1) << 20)
-                                                                           : (32u << 20);
+  // (BGZF and BAM alike: one wavefront inflates one block, so a chunk should hold a few thousand blocks)
+  size_t chunk = kind == InputPath::Plain || bgzf_blocks(kind) ? (size_t)std::min<unsigned long long>(128u << 20, ((bytes >> 20) + 1) << 20)
+                                                               : (32u << 20);
   if (o.chunk) chunk = o.chunk;
   // (a deflate block's text has to fit the text buffer: zlib's blocks hold 16 Ki symbols, a few hundred KiB of FASTQ)
   if (kind == InputPath::GzipDevice) chunk = std::max<size_t>(chunk, 1u << 20);
@@ -788,7 +840,7 @@ Sizes sizes_for(const Options& o, InputPath kind, unsigned long long bytes) {
   Sizes z = {chunk, chunk, o.gz_span ? o.gz_span : chunk / 8};
   // BGZF chunks are cut at block boundaries: text of at most `fill_cap` bytes, but always a whole block, so the
   // buffers hold at least the largest block there can be
-  if (kind == InputPath::BgzfDevice) z.chunk = std::max<size_t>(chunk, 65536 + 16);
+  if (bgzf_blocks(kind)) z.chunk = std::max<size_t>(chunk, 65536 + 16);
   return z;
 }
 
@@ -807,11 +859,21 @@ Options read_options() {
 
 // A .gz file that is BGZF through and through is inflated on the device, block by block (BC_GZ_DEVICE=0: never); every
 // other one is a single zlib stream on the host, or with BC_GZ_DEVICE=all goes to the device as well, span by span.
-// false: the name is neither *.fastq nor *.fastq.gz (input.rs:34-39).
-bool decide_path(const std::string& path, Options::GzDevice mode, std::vector<BgzfMember>* members, uint64_t* inflated, InputPath* kind) {
+// A *.bam file always goes the device way, whatever BC_GZ_DEVICE says (that switch is about .gz names); one that is not
+// BGZF, or cannot be read, leaves the reason in *bam_error.
+// false: the name is none of *.fastq, *.fastq.gz and *.bam (input.rs:34-39).
+bool decide_path(const std::string& path, Options::GzDevice mode, std::vector<BgzfMember>* members, uint64_t* inflated, InputPath* kind,
+                 std::string* bam_error) {
   *kind = InputPath::Plain;
-  if (!ends_with(path, "fastq.gz")) return ends_with(path, "fastq");
   std::string why;
+  if (ends_with(path, ".bam")) {
+    *kind = InputPath::BamDevice;
+    const int rc = bgzf_index(path, members, inflated, &why);
+    if (rc < 0) *bam_error = "Failed to open file: " + path;
+    if (rc > 0) *bam_error = "not a BAM file: " + path + " is not BGZF: " + why;
+    return true;
+  }
+  if (!ends_with(path, "fastq.gz")) return ends_with(path, "fastq");
   if (mode != Options::GzDevice::Never && bgzf_index(path, members, inflated, &why) == 0)
     *kind = InputPath::BgzfDevice;
   else
@@ -835,7 +897,12 @@ bool plan_shard(InputPath kind, Source& src, const std::vector<BgzfMember>& memb
   const bool last_shard = shard + 1 == n_shards;
   p->text_b = inflated;
   p->end_member = members.size();
-  if (kind == InputPath::BgzfDevice) {
+  if (kind == InputPath::BamDevice) {
+    // (text_a: the first record's offset, set by the caller.)  The blocks from the one that holds it on; a BAM file
+    // cannot be entered in the middle without walking its records, so its first shard takes all of it
+    p->nothing = shard != 0;
+    p->first_member = members.empty() ? 0 : bgzf_shard_members(members, p->text_a, p->text_b, 1, 2).first_member;  // (as a last shard's)
+  } else if (kind == InputPath::BgzfDevice) {
     if (n_shards > 1) {
       BgzfHostReader hr;
       hr.fd = src.fd;
@@ -876,7 +943,7 @@ bool plan_shard(InputPath kind, Source& src, const std::vector<BgzfMember>& memb
 
 std::unique_ptr<Producer> make_producer(Ingest& in, Source& src, const std::vector<BgzfMember>& members, const ShardPlan& sp,
                                         const Options& opt, const Sizes& sz, int device, GzDevStats* gzs) {
-  if (in.kind == InputPath::BgzfDevice) {
+  if (bgzf_blocks(in.kind)) {
     auto p = std::make_unique<BgzfProducer>(src, members, in.path);
     p->fill_cap = sz.fill_cap;
     p->chunk = in.chunk;
@@ -933,7 +1000,8 @@ int acquire_buffers(int device, size_t chunk, InputPath kind, size_t gz_comp_cap
     }
     if (rc == BC_OK) rc = g_cached->alloc();
   }
-  if (rc == BC_OK && kind == InputPath::BgzfDevice) rc = g_cached->alloc_bgzf();
+  if (rc == BC_OK && bgzf_blocks(kind)) rc = g_cached->alloc_bgzf();
+  if (rc == BC_OK && kind == InputPath::BamDevice) rc = g_cached->alloc_bam();
   if (rc == BC_OK && kind == InputPath::GzipDevice) rc = g_cached->alloc_gzdev(gz_comp_cap);
   if (rc != BC_OK) {
     drop_cached();
@@ -1089,8 +1157,13 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   std::vector<BgzfMember> members;
   uint64_t inflated = 0;
   InputPath kind;
-  if (!decide_path(path, opt.gz_device, &members, &inflated, &kind)) {
+  std::string bam_error;
+  if (!decide_path(path, opt.gz_device, &members, &inflated, &kind, &bam_error)) {
     set_error("This program only works with *.fastq files and *.fastq.gz files.  The latter is still experimental");
+    return BC_ERR_INVALID;
+  }
+  if (!bam_error.empty()) {
+    set_error(bam_error);
     return BC_ERR_INVALID;
   }
   Source src;
@@ -1127,13 +1200,23 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   }
   const bool last_shard = shard + 1 == n_shards;
   ShardPlan sp;
+  uint32_t n_ref = 0;
+  if (kind == InputPath::BamDevice) {  // the header is the host's: the framing starts behind it
+    uint64_t first_record = 0;
+    std::string why;
+    if (!bam_header(src.fd, members, inflated, &n_ref, &first_record, &why)) {
+      set_error("not a BAM file: " + path + ": " + why);
+      return finish(BC_ERR_INVALID);
+    }
+    sp.text_a = first_record;
+  }
   if (!plan_shard(kind, src, members, inflated, shard, n_shards, &sp)) {
     set_error("no FASTQ record boundary found near a shard boundary of " + path + " (read error, or not 4-line FASTQ)");
     return finish(BC_ERR_INVALID);
   }
   if (sp.nothing) return finish(BC_OK);
   src.threads = opt.threads;
-  const Sizes sz = sizes_for(opt, kind, kind == InputPath::BgzfDevice ? sp.text_b - sp.text_a : src.size);
+  const Sizes sz = sizes_for(opt, kind, bgzf_blocks(kind) ? sp.text_b - sp.text_a : src.size);
 
   std::unique_lock<std::mutex> whole_call(g_mu);
   const int device = bc_engine_device(e);
@@ -1144,6 +1227,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   int rc = acquire_buffers(device, sz.chunk, kind, sz.chunk + sz.gz_span + 65536, &in);
   if (rc != BC_OK) return finish(rc);
   in->begin_call(e, kind, &members, path);
+  in->n_ref = n_ref;
   if ((rc = in->set_start(sp.text_a)) != BC_OK) return finish(rc);  // (text_a: a BGZF shard's first record, 0 otherwise)
 
   // the producer runs ahead of the device by the slots that are free: its thread fills, this thread frames
@@ -1152,7 +1236,8 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   std::thread producer_thread([&] { produce(*producer, in->slot, h); });
 
   uint64_t lines_after_last_record = 0;
-  bool test = shard == 0;  // (the file's first record is the first shard's)
+  bool test = shard == 0 && kind != InputPath::BamDevice;  // (the file's first record is the first shard's)
+  unsigned long long bam_left = 0;  // BAM: bytes behind the last whole record of the last chunk counted
   int pending = -1;  // chunk framed but not yet submitted
   int last_counted_slot = -1;  // slot of the last chunk whose records were counted (its text is still on the device)
   // the pending chunk: its stats are in (or about to be); its records go to the engine and into the total
@@ -1165,6 +1250,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
     if (progress && n_rec) progress(total - total % 10000, user);  // the reference prints every 10,000 reads (input.rs:54-57)
     const ChunkStats& cs = *in->slot[b].stats;
     lines_after_last_record = cs.n_lines - 4 * cs.n_rec;
+    bam_left = in->s_text_len[b] - cs.end_pos;
     last_counted_slot = b;
     pending = -1;
     return BC_OK;
@@ -1201,7 +1287,7 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
       }
       rc = in->frame(i % kSlots, i > 0 ? &in->slot[(i - 1) % kSlots] : nullptr);
       if (rc != BC_OK) break;
-    } else if (kind == InputPath::BgzfDevice && s.nblk) {
+    } else if (bgzf_blocks(kind) && s.nblk) {
       if (!eof) {  // (thousands of empty blocks in a row, in the middle of the file)
         set_error("a BGZF chunk of " + path + " holds no text: not supported by the engine");
         rc = BC_ERR_UNSUPPORTED;
@@ -1231,6 +1317,14 @@ static int fastq_count_impl(bc_engine* e, const char* fastq_path, uint32_t shard
   producer_thread.join();
   if (kind == InputPath::GzipDevice) engine_add_gz_segments(e, gzs.segments);
   if (rc != BC_OK) return finish(rc);
+  if (kind == InputPath::BamDevice) {  // every whole record is one read; the file has to end with one
+    if (bam_left) {
+      set_error("read error in " + path + ": the file ends inside a BAM record (" + std::to_string(bam_left) + " bytes behind the last whole one)");
+      return finish(BC_ERR_INVALID);
+    }
+    if (total_reads) *total_reads = total;
+    return finish(BC_OK);
+  }
 
   // what is left after the last whole record: fewer than four complete lines, the ones the reference's reader would have
   // been handed (gz without a final newline: the unterminated last line was given its newline above, so it is among the

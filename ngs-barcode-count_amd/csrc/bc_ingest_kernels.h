@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bc_bgzf.hpp"
+
 namespace {
 
 constexpr uint32_t kScanBlock = 4096;  // text bytes per 256-thread block of the newline kernels (16 per thread)
@@ -18,7 +20,7 @@ struct ChunkStats {
   unsigned int max_qlen;
   unsigned int qual_differs;   // some record's quality line is not as long as its sequence line
   unsigned int last_is_newline;
-  unsigned int pad;
+  unsigned int pad;            // BAM: the framing's status (kBam* of bc_bam.h)
 };
 
 struct DevState {
@@ -214,6 +216,19 @@ __global__ void ingest_overlap_kernel(const uint8_t* __restrict__ prev_end, uint
   // copies the `bytes` bytes that end at prev_end to the `bytes` bytes that end at dst_end
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < bytes) dst_end[-(long long)bytes + i] = prev_end[-(long long)bytes + i];
+}
+
+// BAM: what the framing of bc_bam.hip found, as the stats of a chunk whose every record has four lines
+__global__ void ingest_from_bam_kernel(const bc::BamStats* fs, ChunkStats* cs) {
+  cs->start = fs->start;
+  cs->n_rec = fs->n_rec;
+  cs->n_lines = 4ull * fs->n_rec;
+  cs->end_pos = fs->end_pos;
+  cs->min_len = fs->min_len;
+  cs->max_len = cs->max_qlen = fs->max_len;
+  cs->qual_differs = 0;
+  cs->last_is_newline = 1;
+  cs->pad = fs->status;
 }
 
 __global__ void ingest_advance_kernel(DevState* st, const ChunkStats* cs, unsigned long long buf_file_off) {
