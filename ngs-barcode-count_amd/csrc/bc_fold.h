@@ -6,8 +6,9 @@
 //   bc_fold_scan     bucket starts, and the fold's work items (bucket x chunk of entries)
 //   bc_fold_scatter  the log grouped by bucket: 16384-entry tiles sorted in LDS, then written out as runs
 //                    (the tile held in registers meanwhile, the next tile's loads in flight)
-//   bc_fold_apply    per item and quarter of its bucket: 128 KB of bit map into LDS, one LDS atomicOr per entry (a bit
-//                    that was set already makes the entry a table add), the quarter written back
+//   bc_fold_apply    per item and quarter of its bucket (one such unit per workgroup and step, the four of an item on
+//                    four workgroups of one XCD at one time: fold_apply_unit): 128 KB of bit map into LDS, one LDS
+//                    atomicOr per entry (a bit that was set already makes the entry a table add), the quarter written back
 // A tuple with c entries ends as the atomic path would leave it: bit clear before -> bit set and table + c - 1; bit set
 // before -> table + c.  A bucket with more than kFoldChunk entries (a hot library) is split over several items, which
 // then meet on the same quarter: there the first entry of a tuple in an item also sets its bit in memory, with a
@@ -24,6 +25,8 @@
 // item -- the empty ones, and the split ones, whose items meet in memory.  Every word of the map is defined afterwards.
 #pragma once
 
+#include "bc_intrin.h"
+
 namespace bc {
 
 constexpr uint32_t kFoldTPB = 1024;
@@ -37,6 +40,39 @@ constexpr uint32_t kFoldQuarterWords = 1u << (kFoldQuarterShift - 5);
 constexpr uint32_t kFoldSpare = 64;          // bc_fold_scatter: bins behind the buckets' for kLogNone entries, one per lane
 constexpr uint32_t kFoldScatterLds = kFoldTile * 4u + (3u * kFoldMaxBuckets + 2u * kFoldSpare) * 4u;
 constexpr uint32_t kFoldApplyLds = kFoldQuarterWords * 4u;
+constexpr uint32_t kFoldXcds = 8;            // bc_fold_apply: workgroups b and b + 8 are observed to share an L2
+
+// bc_fold_apply's unit of work is one quarter of one item's bucket; a workgroup walks the units of step 0, 1, ... until
+// one is not valid (the items of a workgroup rise with the step).  Over the blocks of a grid and their steps every
+// (item < n_items, quarter < kFoldQuarters) comes up exactly once, for every grid >= 1.  A grid that is a multiple of
+// 32 puts the four quarters of an item on blocks 8 apart, which are observed to be dealt to one XCD, and in the same
+// step.  The intent is that the four read the item's entries at about the same time, so that one reading comes from
+// HBM and three can be served by that XCD's L2 (what the counters say of it: DESIGN.md 8).  That is a matter of speed
+// alone: the four exchange nothing and write disjoint quarters.
+struct FoldUnit {
+  uint32_t item, quarter;
+  bool valid;
+};
+BC_HD FoldUnit fold_apply_unit(uint32_t block, uint32_t grid, uint32_t step, uint32_t n_items) {
+  uint64_t item;
+  uint32_t quarter;
+  if (grid % (kFoldXcds * kFoldQuarters) == 0u) {
+    const uint32_t xcd = block % kFoldXcds, slot = block / kFoldXcds;
+    quarter = slot % kFoldQuarters;
+    item = (uint64_t)(slot / kFoldQuarters) * kFoldXcds + xcd + (uint64_t)step * (grid / kFoldQuarters);
+  } else {
+    const uint64_t u = block + (uint64_t)step * grid;
+    quarter = (uint32_t)(u % kFoldQuarters);
+    item = u / kFoldQuarters;
+  }
+  FoldUnit r;
+  r.valid = item < n_items;
+  r.item = r.valid ? (uint32_t)item : 0u;
+  r.quarter = quarter;
+  return r;
+}
+
+#if defined(__HIPCC__)
 
 // A workgroup barrier that orders LDS alone: loads, stores and atomics to global memory that are in flight stay in
 // flight across it (__syncthreads waits for them).  Scatter and apply place every wait for memory themselves: both
@@ -238,10 +274,12 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_zero_unowned(uint32_t nb, co
 
 // n_words: bit-map words in use (ceil(entries / 32)); dirty: the table's dirty-block map, or null; fresh: the map counts
 // as all zero whatever memory holds (the owner of a bucket does not load it; bc_fold_zero_unowned has run).
-// A workgroup's entries arrive in batches of sixteen per thread, and a batch is requested before the one ahead of it is
-// processed: the next batch of the quarter, else the first batch of the next quarter (the same entries again, from the
-// L2), else the first batch of the workgroup's next item -- none of which depends on what LDS holds, so they stay in
-// flight across the barriers (fold_lds_barrier).  Every request is clipped to its item.
+// A workgroup works on one unit at a time, a quarter of an item's bucket (fold_apply_unit), and reads the item's entries
+// for it; the units of the other quarters read the same entries elsewhere, in the same step of their workgroups.
+// The entries arrive in batches of sixteen per thread, and a batch is requested before the one ahead of it is
+// processed: the next batch of the unit, else the first batch of the workgroup's next unit -- neither of which depends
+// on what LDS holds, so they stay in flight across the barriers (fold_lds_barrier).  Every request is clipped to its
+// item.
 __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __restrict__ grouped, uint32_t nb,
                                                          const uint32_t* __restrict__ start, const uint32_t* __restrict__ item_off,
                                                          uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ table,
@@ -249,7 +287,7 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
   static_assert(kFoldMaxBuckets <= kFoldTPB, "one bucket per thread");
   extern __shared__ uint32_t fold_smem[];
   uint4* q4 = reinterpret_cast<uint4*>(fold_smem);
-  // the item in turn and the workgroup's next one: bucket, sole item of its bucket, first entry, end of its entries
+  // the item of the unit in turn and of the workgroup's next one: bucket, sole item of its bucket, first entry, end of its entries
   __shared__ uint32_t s_item[2][4];
   const uint32_t tid = threadIdx.x;
   constexpr uint32_t kPer = kFoldQuarterWords / 4u / kFoldTPB;  // uint4 per thread
@@ -257,8 +295,8 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
   constexpr uint32_t kBatch = kIn4 * 4u * kFoldTPB;
   const uint4 none4 = make_uint4(kLogNone, kLogNone, kLogNone, kLogNone);
   const uint32_t n_items = item_off[nb];
-  uint32_t it = blockIdx.x;
-  if (it >= n_items) return;
+  FoldUnit u = fold_apply_unit(blockIdx.x, gridDim.x, 0u, n_items);
+  if (!u.valid) return;
   auto add = [&](uint32_t idx) {
     table_add(&table[idx]);
     if (dirty) dirty[idx >> 6] = (uint8_t)1;
@@ -287,119 +325,130 @@ __global__ __launch_bounds__(kFoldTPB) void bc_fold_apply(const uint32_t* __rest
       d[k] = g4[i4 < last ? i4 : last];
     }
   };
-  publish(it, 0u);
+  publish(u.item, 0u);
   fold_lds_barrier();
   uint4 cur[kIn4], nxt[kIn4];
   request(cur, item_word(0u, 2u) & ~3u, item_word(0u, 3u));
-  for (uint32_t slot = 0; it < n_items; it += gridDim.x, slot ^= 1u) {
-    const uint32_t b = item_word(slot, 0u);
+  for (uint32_t step = 0, slot = 0; u.valid; ++step, slot ^= 1u) {
+    const uint32_t b = item_word(slot, 0u), quarter = u.quarter;
     const bool owner = item_word(slot, 1u) != 0u;
     const uint32_t e_lo = item_word(slot, 2u), e_end = item_word(slot, 3u), first = e_lo & ~3u;
-    // (the other slot was last read before this item's predecessor passed its barriers; read again behind this item's)
-    const bool more = it + gridDim.x < n_items;
-    if (more) publish(it + gridDim.x, slot ^ 1u);
-    // the bucket's quarters one after the other, as far as the table reaches (no entry can fall past its end): the
-    // item's entries are read once per quarter, from the L2
+    // (the other slot was last read before this unit's predecessor passed its barriers; read again behind this unit's)
+    u = fold_apply_unit(blockIdx.x, gridDim.x, step + 1u, n_items);
+    const bool more = u.valid;
+    if (more) publish(u.item, slot ^ 1u);
+    // the bucket's quarters as far as the table reaches (no entry can fall past its end); a unit past them has nothing
+    // to do but to request the next one's entries.  Its own first batch, requested one unit ahead, was read for nothing
+    // and the next unit's request is not ahead of anything: at most three units of a fold (the last bucket's), which
+    // the walk would have to know the table's end to leave out
     const uint64_t wb = (uint64_t)b << (kFoldBucketShift - 5);
     const uint64_t left = n_words - wb;
     const uint32_t n_q = left >= (uint64_t)kFoldQuarters * kFoldQuarterWords
                              ? kFoldQuarters : (uint32_t)((left + kFoldQuarterWords - 1u) / kFoldQuarterWords);
-    for (uint32_t quarter = 0; quarter < n_q; ++quarter) {
-      const uint64_t w0 = wb + (uint64_t)quarter * kFoldQuarterWords;
-      const uint32_t nw = n_words - w0 < kFoldQuarterWords ? (uint32_t)(n_words - w0) : kFoldQuarterWords;
-      uint32_t* gw = bits + w0;
-      if (fresh && owner) {
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) q4[k * kFoldTPB + tid] = make_uint4(0u, 0u, 0u, 0u);
-      } else if (nw == kFoldQuarterWords) {
-        // a whole quarter: its loads together, one wait
-        uint4 v[kPer];
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) v[k] = reinterpret_cast<const uint4*>(gw)[k * kFoldTPB + tid];
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) q4[k * kFoldTPB + tid] = v[k];
-      } else {
-        // the table's ragged last quarter
-#pragma unroll 1
-        for (uint32_t k = 0; k < kPer; ++k) {
-          const uint32_t w = (k * kFoldTPB + tid) * 4u;
-          uint4 v;
-          if (w + 4u <= nw) {
-            v = reinterpret_cast<const uint4*>(gw)[w / 4u];
-          } else {
-            v.x = w + 0u < nw ? gw[w + 0u] : 0u;
-            v.y = w + 1u < nw ? gw[w + 1u] : 0u;
-            v.z = w + 2u < nw ? gw[w + 2u] : 0u;
-            v.w = w + 3u < nw ? gw[w + 3u] : 0u;
-          }
-          q4[w / 4u] = v;
-        }
-      }
+    if (quarter >= n_q) {
       fold_lds_barrier();
-      for (uint32_t i0 = first; i0 < e_end; i0 += kBatch) {
-        if (e_end - i0 > kBatch) {
-          request(nxt, i0 + kBatch, e_end);
-        } else if (quarter + 1u < n_q) {
-          request(nxt, first, e_end);
-        } else if (more) {
-          request(nxt, item_word(slot ^ 1u, 2u) & ~3u, item_word(slot ^ 1u, 3u));
-        } else {
-#pragma unroll
-          for (uint32_t k = 0; k < kIn4; ++k) nxt[k] = none4;
-        }
-        // the batch's sixteen LDS atomics back to back, one wait: an entry of another quarter, or outside the item, ORs
-        // nothing into a word of the thread's own (no two lanes of a wave meet there)
-        const uint32_t x[kIn4 * 4] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
-                                      cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
-        uint32_t old[kIn4 * 4], mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kIn4 * 4; ++k) {
-          const uint32_t i = i0 + ((k / 4u) * kFoldTPB + tid) * 4u + (k & 3u);
-          const bool on = i >= e_lo && i < e_end && ((x[k] >> kFoldQuarterShift) & (kFoldQuarters - 1u)) == quarter;
-          mine |= (on ? 1u : 0u) << k;
-          old[k] = atomicOr(&fold_smem[on ? (x[k] >> 5) & (kFoldQuarterWords - 1u) : tid], on ? 1u << (x[k] & 31u) : 0u);
-        }
-        // the two rare follow-ups, one entry at a time: a bit that was set already makes the entry a table add.  A split
-        // bucket: the first of the item's entries claims the bit in memory at once; another item may have been first (a
-        // repeat after all)
-        uint32_t again = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kIn4 * 4; ++k) again |= ((old[k] >> (x[k] & 31u)) & 1u) << k;
-        again &= mine;
-        uint32_t todo = owner ? again : mine;
-        while (todo) {
-          const uint32_t k = (uint32_t)__builtin_ctz(todo);
-          todo &= todo - 1u;
-          uint32_t v = x[0];
-#pragma unroll
-          for (uint32_t j = 1; j < kIn4 * 4; ++j) v = k == j ? x[j] : v;
-          const uint32_t m = 1u << (v & 31u);
-          if (((again >> k) & 1u) || (atomicOr(&gw[(v >> 5) & (kFoldQuarterWords - 1u)], m) & m)) add(v);
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kIn4; ++k) cur[k] = nxt[k];
-      }
-      fold_lds_barrier();
-      // the owner writes its quarter back as it is now (nearly every line of it changed for a sparse batch)
-      if (owner && nw == kFoldQuarterWords) {
-#pragma unroll
-        for (uint32_t k = 0; k < kPer; ++k) reinterpret_cast<uint4*>(gw)[k * kFoldTPB + tid] = q4[k * kFoldTPB + tid];
-      } else if (owner) {
-#pragma unroll 1
-        for (uint32_t k = 0; k < kPer; ++k) {
-          const uint32_t w = (k * kFoldTPB + tid) * 4u;
-          const uint4 c = q4[w / 4u];
-          if (w + 4u <= nw) {
-            reinterpret_cast<uint4*>(gw)[w / 4u] = c;
-          } else {
-            if (w + 0u < nw) gw[w + 0u] = c.x;
-            if (w + 1u < nw) gw[w + 1u] = c.y;
-            if (w + 2u < nw) gw[w + 2u] = c.z;
-          }
-        }
-      }
-      fold_lds_barrier();
+      if (more) request(cur, item_word(slot ^ 1u, 2u) & ~3u, item_word(slot ^ 1u, 3u));
+      continue;
     }
+    const uint64_t w0 = wb + (uint64_t)quarter * kFoldQuarterWords;
+    const uint32_t nw = n_words - w0 < kFoldQuarterWords ? (uint32_t)(n_words - w0) : kFoldQuarterWords;
+    uint32_t* gw = bits + w0;
+    if (fresh && owner) {
+#pragma unroll
+      for (uint32_t k = 0; k < kPer; ++k) q4[k * kFoldTPB + tid] = make_uint4(0u, 0u, 0u, 0u);
+    } else if (nw == kFoldQuarterWords) {
+      // a whole quarter: its loads together, one wait
+      uint4 v[kPer];
+#pragma unroll
+      for (uint32_t k = 0; k < kPer; ++k) v[k] = reinterpret_cast<const uint4*>(gw)[k * kFoldTPB + tid];
+#pragma unroll
+      for (uint32_t k = 0; k < kPer; ++k) q4[k * kFoldTPB + tid] = v[k];
+    } else {
+      // the table's ragged last quarter
+#pragma unroll 1
+      for (uint32_t k = 0; k < kPer; ++k) {
+        const uint32_t w = (k * kFoldTPB + tid) * 4u;
+        uint4 v;
+        if (w + 4u <= nw) {
+          v = reinterpret_cast<const uint4*>(gw)[w / 4u];
+        } else {
+          v.x = w + 0u < nw ? gw[w + 0u] : 0u;
+          v.y = w + 1u < nw ? gw[w + 1u] : 0u;
+          v.z = w + 2u < nw ? gw[w + 2u] : 0u;
+          v.w = w + 3u < nw ? gw[w + 3u] : 0u;
+        }
+        q4[w / 4u] = v;
+      }
+    }
+    fold_lds_barrier();
+    for (uint32_t i0 = first; i0 < e_end; i0 += kBatch) {
+      if (e_end - i0 > kBatch) {
+        request(nxt, i0 + kBatch, e_end);
+      } else if (more) {
+        request(nxt, item_word(slot ^ 1u, 2u) & ~3u, item_word(slot ^ 1u, 3u));
+      } else {
+#pragma unroll
+        for (uint32_t k = 0; k < kIn4; ++k) nxt[k] = none4;
+      }
+      // the batch's sixteen LDS atomics back to back, one wait: an entry of another quarter, or outside the item, ORs
+      // nothing into a word of the thread's own (no two lanes of a wave meet there)
+      const uint32_t x[kIn4 * 4] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w,
+                                    cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
+      uint32_t old[kIn4 * 4], mine = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kIn4 * 4; ++k) {
+        const uint32_t i = i0 + ((k / 4u) * kFoldTPB + tid) * 4u + (k & 3u);
+        const bool on = i >= e_lo && i < e_end && ((x[k] >> kFoldQuarterShift) & (kFoldQuarters - 1u)) == quarter;
+        mine |= (on ? 1u : 0u) << k;
+        old[k] = atomicOr(&fold_smem[on ? (x[k] >> 5) & (kFoldQuarterWords - 1u) : tid], on ? 1u << (x[k] & 31u) : 0u);
+      }
+      // the two rare follow-ups, one entry at a time: a bit that was set already makes the entry a table add.  A split
+      // bucket: the first of the item's entries claims the bit in memory at once; another item may have been first (a
+      // repeat after all)
+      uint32_t again = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kIn4 * 4; ++k) again |= ((old[k] >> (x[k] & 31u)) & 1u) << k;
+      again &= mine;
+      uint32_t todo = owner ? again : mine;
+      while (todo) {
+        const uint32_t k = (uint32_t)__builtin_ctz(todo);
+        todo &= todo - 1u;
+        uint32_t v = x[0];
+#pragma unroll
+        for (uint32_t j = 1; j < kIn4 * 4; ++j) v = k == j ? x[j] : v;
+        const uint32_t m = 1u << (v & 31u);
+        if (((again >> k) & 1u) || (atomicOr(&gw[(v >> 5) & (kFoldQuarterWords - 1u)], m) & m)) add(v);
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kIn4; ++k) cur[k] = nxt[k];
+    }
+    fold_lds_barrier();
+    // the owner writes its quarter back as it is now (nearly every line of it changed for a sparse batch), with
+    // non-temporal stores: nobody reads these 128 KB again soon, and the L2 they pass through holds the entries that
+    // the units of the other quarters are still reading
+    if (owner && nw == kFoldQuarterWords) {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+      for (uint32_t k = 0; k < kPer; ++k) {
+        const uint4 c = q4[k * kFoldTPB + tid];
+        const u32x4 cv = {c.x, c.y, c.z, c.w};
+        __builtin_nontemporal_store(cv, reinterpret_cast<u32x4*>(gw) + k * kFoldTPB + tid);
+      }
+    } else if (owner) {
+#pragma unroll 1
+      for (uint32_t k = 0; k < kPer; ++k) {
+        const uint32_t w = (k * kFoldTPB + tid) * 4u;
+        const uint4 c = q4[w / 4u];
+        if (w + 4u <= nw) {
+          reinterpret_cast<uint4*>(gw)[w / 4u] = c;
+        } else {
+          if (w + 0u < nw) gw[w + 0u] = c.x;
+          if (w + 1u < nw) gw[w + 1u] = c.y;
+          if (w + 2u < nw) gw[w + 2u] = c.z;
+        }
+      }
+    }
+    fold_lds_barrier();
   }
 }
 
@@ -437,10 +486,17 @@ inline hipError_t fold_launch(hipStream_t stream, const uint32_t* log, uint64_t 
                        (const uint32_t*)item_off, bits, n_words);
   }
   const uint64_t items_max = (n + kFoldChunk - 1) / kFoldChunk + nb;
-  if (!apply_grid) apply_grid = (uint32_t)(items_max < n_cus ? items_max : n_cus);
+  if (!apply_grid) {
+    // one workgroup per CU, in whole sibling groups where the device has that many CUs (fold_apply_unit)
+    const uint64_t units_max = items_max * kFoldQuarters, group = kFoldXcds * kFoldQuarters;
+    const uint64_t cus = n_cus >= group ? n_cus - n_cus % group : n_cus;
+    apply_grid = (uint32_t)(units_max < cus ? units_max : cus);
+  }
   hipLaunchKernelGGL(bc_fold_apply, dim3(apply_grid), dim3(kFoldTPB), kFoldApplyLds, stream, (const uint32_t*)grouped, nb,
                      (const uint32_t*)start, (const uint32_t*)item_off, bits, n_words, table, dirty, fresh ? 1u : 0u);
   return hipGetLastError();
 }
+
+#endif  // __HIPCC__
 
 }  // namespace bc
