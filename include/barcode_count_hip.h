@@ -100,6 +100,26 @@ int bc_plan_set_min_quality(bc_plan *p, float min_quality);
  * bases: low quality <=> sum(scores) < T_n */
 uint32_t bc_plan_quality_threshold(const bc_plan *p, uint32_t run_len);
 
+/* Which orientation of a read is counted (the reference has no such option; MAGeCK's --reverse-complement is one).
+ * rc(read): the sequence line reversed over its own length, every byte through the complement table -- the IUPAC pairs
+ * A-T C-G M-K R-Y V-B H-D in either case; W S N w s n and every other byte (>= 0x80 included) map to themselves -- and
+ * the quality line reversed over ITS own length (the two can differ, bc_engine_submit_device_q).  It is what the BAM
+ * path hands on for a record flagged 0x10 and what `samtools fastq` writes for it.
+ *   BC_STRAND_FORWARD (default): reads are counted as they stand.
+ *   BC_STRAND_REVERSE: every read is counted as rc(read); nothing else changes.
+ *   BC_STRAND_BOTH: a read is judged as it stands first.  Any outcome but BC_CONSTANT_REGION is its outcome -- forward
+ *     wins, even where rc(read) would match too; a BC_CONSTANT_REGION read's outcome is that of rc(read), whatever that
+ *     is (BC_CONSTANT_REGION again is possible).
+ * Every read adds one to BC_TOTAL_READS and one to exactly one other counter; bc_engine_counters never shows a read
+ * twice.  Both orientations count into one Results: a random-barcode key seen forward makes the same molecule seen in
+ * reverse a duplicate.  For unaligned BAM from a basecaller (no 0x10 flags), non-directional amplicon preps, or an R2
+ * file.  BC_ERR_INVALID for another value.  Read when an engine is created: a later change does not reach that engine. */
+#define BC_STRAND_FORWARD 0
+#define BC_STRAND_REVERSE 1
+#define BC_STRAND_BOTH 2
+int bc_plan_set_strand(bc_plan *p, int strand);
+int bc_plan_strand(const bc_plan *p);
+
 /* ---- engine ---------------------------------------------------------------------------- */
 
 /* Number of u32 entries of the dense per-(sample, barcode tuple) counter table the plan needs
@@ -118,7 +138,12 @@ void bc_engine_destroy(bc_engine *e);
  * Layout: read i occupies bytes [i*stride, i*stride+len_i) of `seq` and of `qual`
  * (ASCII, as in the FASTQ); len_i = lens[i] or read_len when lens is NULL.  qual may be NULL
  * only when the quality filter is off.  Both buffers must be 16-byte aligned.
- * _device: pointers are device memory; the call only enqueues work on the engine's stream.
+ * _device: pointers are device memory; the call only enqueues work on the engine's stream -- under BC_STRAND_FORWARD and
+ * BC_STRAND_REVERSE.  Under BC_STRAND_BOTH it no longer "only enqueues": per chunk of BC_STRAND_CHUNK reads (default
+ * 2^24, a multiple of 256) the host waits once for the first pass, to learn how many reads go to the second; the
+ * caller's buffers are still read after the call returns (the last chunk's second pass), as before.
+ * The engine's scratch for the reversed reads grows on demand to one chunk -- per read 2 * stride + 4 bytes, and with
+ * BC_STRAND_BOTH 13 more (the list, the outcome byte, the index the traced kernels write) -- and is freed with it.
  * _host: pointers are host memory; the engine stages them through pinned buffers with
  * hipMemcpyAsync on a side stream and returns when the host buffers may be reused. */
 int bc_engine_submit_device(bc_engine *e, const void *d_seq, const void *d_qual, const void *d_lens, uint32_t stride,
@@ -435,8 +460,15 @@ const bc_plan *bc_engine_plan(const bc_engine *e);
 
 /* Debug / parity-test hook: the next submits also write, for read i of the submit, its outcome
  * (BC_* counter index; BC_MATCHED = passed every test) to d_outcome_u8[i] and its dense table index
- * to d_index_u64[i].  Both device pointers; NULL switches tracing off. */
+ * to d_index_u64[i].  Both device pointers; NULL switches tracing off.  Under BC_STRAND_REVERSE / _BOTH read i receives
+ * its FINAL outcome and index at its own position i, whichever orientation decided it. */
 int bc_engine_trace(bc_engine *e, void *d_outcome_u8, void *d_index_u64);
+/* The reads handed to the reverse pass since the engine was created -- all of them under BC_STRAND_REVERSE, the forward
+ * constant-region failures under BC_STRAND_BOTH, 0 under BC_STRAND_FORWARD -- and how many of those ended BC_MATCHED.
+ * (Under a random-barcode plan either sighting of a molecule may be the BC_MATCHED one, so the second number depends on
+ * the order the device counted them in; the counters and rows do not.)  Neither is zeroed by a reset.  Either pointer may be NULL.  Waits for the engine's stream (the two numbers are kept on
+ * the device), except under BC_STRAND_FORWARD. */
+int bc_engine_strand_reads(const bc_engine *e, uint64_t *retried, uint64_t *matched_reverse);
 
 /* HIP-event timing of the match/count kernel on the engine's stream (for the roofline) */
 int bc_engine_timing(bc_engine *e, int enable);
@@ -654,6 +686,21 @@ typedef struct bc_bam_frame_result {
 int bc_bam_frame_device(int device_id, void *hip_stream, const void *d_text, uint64_t len, uint64_t start, uint32_t n_ref,
                         uint32_t *d_rec_at, uint32_t *d_rec_len, uint32_t *d_rec_flag, uint64_t capacity,
                         bc_bam_frame_result *result);
+
+/* ---- reverse complement of a batch on the device ------------------------------------------------- */
+
+/* The kernel behind BC_STRAND_REVERSE / _BOTH on its own: output read j = rc(read d_index[j]) of the batch (d_index: u32,
+ * device memory, may repeat, skip and reorder; NULL = reads 0 .. n_out in order), rc as bc_plan_set_strand defines it.
+ * The batch has the layout bc_engine_submit_device[_q] takes (d_qual, d_lens, d_qlens may be NULL; without d_lens every
+ * read is read_len long; without d_qlens a quality line is as long as its sequence line), and the output has the same
+ * form at the same stride: d_seq_out (and d_qual_out, d_lens_out, d_qlens_out for every input given) hold n_out reads.
+ * Bytes [len, stride) of an output line are padding as the BAM path pads: 'N' in a sequence line, '!' in a quality line;
+ * nothing outside the n_out * stride bytes is written.  Sequence and quality buffers 16-byte aligned; not in place.
+ * Every d_index[j] must name a read of the batch: the call cannot check that.  Only enqueues on hip_stream (NULL: the
+ * default stream) and does not wait. */
+int bc_strand_orient_device(int device_id, void *hip_stream, const void *d_seq, const void *d_qual, const void *d_lens,
+                            const void *d_qlens, uint32_t stride, uint32_t read_len, const uint32_t *d_index, uint64_t n_out,
+                            void *d_seq_out, void *d_qual_out, void *d_lens_out, void *d_qlens_out);
 
 /* ---- synthetic workloads (bench + full-size parity) -------------------------------------- */
 

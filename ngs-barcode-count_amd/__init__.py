@@ -102,6 +102,15 @@ class Plan:
     def set_min_quality(self, q):
         _check(self._lib, self._lib.bc_plan_set_min_quality(self._p, float(q)))
 
+    def set_strand(self, strand):
+        """which orientation of a read is counted: "forward" (default), "reverse" (every read as its reverse
+        complement) or "both" (as it stands first; reversed when the constant region fails).  Read by Engine()."""
+        if strand not in _lib.STRAND_NAMES:
+            raise ValueError("strand must be one of %s, not %r" % (", ".join(_lib.STRAND_NAMES), strand))
+        _check(self._lib, self._lib.bc_plan_set_strand(self._p, _lib.STRAND_NAMES.index(strand)))
+
+    strand = property(lambda s: _lib.STRAND_NAMES[s._lib.bc_plan_strand(s._p)])
+
     max_constant_errors = property(lambda s: s._lib.bc_plan_max_constant_errors(s._p))
     max_sample_errors = property(lambda s: s._lib.bc_plan_max_sample_errors(s._p))
     max_barcode_errors = property(lambda s: [s._lib.bc_plan_max_barcode_errors(s._p, i)
@@ -196,6 +205,14 @@ class Engine:
     def trace(self, d_outcome_u8, d_index_u64):
         """per-read outcome / dense index written by the next submits (tests); None disables"""
         _check(self._lib, self._lib.bc_engine_trace(self._e, d_outcome_u8, d_index_u64))
+
+    def strand_reads(self):
+        """(retried, matched_reverse): the reads handed to the reverse pass since the engine was created (all of them
+        under "reverse", the forward constant-region failures under "both", 0 under "forward") and how many of those
+        matched.  Waits for the engine's stream unless the strand is "forward"."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(self._lib, self._lib.bc_engine_strand_reads(self._e, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # random-barcode mode: the set of (tuple, random barcode) keys
     def key_count(self):
@@ -616,6 +633,15 @@ def bam_scan(path, lib=None):
     n_ref, first, size = C.c_uint32(), C.c_uint64(), C.c_uint64()
     _check(lib, lib.bc_bam_scan(str(path).encode(), C.byref(n_ref), C.byref(first), C.byref(size)))
     return n_ref.value, first.value, size.value
+
+
+def orient_device(d_seq, d_qual, stride, read_len, n_out, d_seq_out, d_qual_out, d_lens=None, d_qlens=None, d_index=None,
+                  d_lens_out=None, d_qlens_out=None, device=0, stream=None, lib=None):
+    """bc_strand_orient_device: output read j = the reverse complement of read d_index[j] (None: read j) of a batch on
+    the device, in the batch's own form.  Device pointers; only enqueues on `stream`."""
+    lib = lib or _lib.load()
+    _check(lib, lib.bc_strand_orient_device(int(device), stream, d_seq, d_qual, d_lens, d_qlens, stride, read_len, d_index,
+                                            n_out, d_seq_out, d_qual_out, d_lens_out, d_qlens_out))
 
 
 def make_set(seed, n, k, min_dist=1, lib=None):

@@ -39,6 +39,8 @@ class BamFrameResult(C.Structure):  # bc_bam_frame_result
                 ("end_pos", C.c_uint64)]
 
 
+BC_STRAND_FORWARD, BC_STRAND_REVERSE, BC_STRAND_BOTH = 0, 1, 2
+STRAND_NAMES = ("forward", "reverse", "both")
 BC_BAM_OK, BC_BAM_BROKEN_CHAIN, BC_BAM_CAPACITY, BC_BAM_TOO_LONG = 0, 1, 2, 3
 BC_GUNZIP_OK, BC_GUNZIP_OUTPUT_FULL, BC_GUNZIP_BAD_STREAM = 0, 1, 2
 INFLATE_STATUS = ["ok", "bad block type", "bad code lengths", "invalid symbol or distance", "input overrun",
@@ -80,6 +82,8 @@ PLAN_API = {
                                  C.POINTER(C.c_uint16)]),
     "bc_plan_set_min_quality": (_int, [_vp, C.c_float]),
     "bc_plan_quality_threshold": (_u32, [_vp, _u32]),
+    "bc_plan_set_strand": (_int, [_vp, _int]),
+    "bc_plan_strand": (_int, [_vp]),
     "bc_plan_table_entries": (_u64, [_vp]),
     "bc_plan_mode": (_int, [_vp]),
 }
@@ -133,6 +137,8 @@ ENGINE_API = {
     "bc_engine_sclk_mhz": (_int, [_vp, C.POINTER(C.c_double)]),
     "bc_plan_precompile": (_int, [_vp, _u32, _u32, _int, _cp]),  # lives with the engine: it drives the device compiler
     "bc_engine_trace": (_int, [_vp, _vp, _vp]),
+    "bc_engine_strand_reads": (_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bc_strand_orient_device": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "bc_engine_row_text": (_int, [_vp, _u64, _cp, _sz, _cp, _sz, C.POINTER(C.c_uint64)]),
     "bc_engine_key_words": (_u32, [_vp]),
     "bc_engine_key_count": (_int, [_vp, C.POINTER(C.c_uint64)]),
@@ -174,9 +180,13 @@ ENGINE_API = {
 }
 
 
-def declare(lib, api):
+def declare(lib, api, strict=True):
     for name, (res, args) in api.items():
-        f = getattr(lib, name)
+        f = getattr(lib, name, None)
+        if f is None and not strict:  # (an older build loaded by path for an A/B: it lacks the newest calls)
+            continue
+        if f is None:
+            raise AttributeError("%s: undefined symbol %s" % (lib._name, name))
         f.restype = res
         f.argtypes = args
     return lib
@@ -203,8 +213,8 @@ def load(path=None):
         if importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
     lib = C.CDLL(p)
-    declare(lib, PLAN_API)
-    declare(lib, ENGINE_API)
+    declare(lib, PLAN_API, strict=path is None)
+    declare(lib, ENGINE_API, strict=path is None)
     if path is None:
         _lib = lib
     return lib

@@ -55,6 +55,10 @@ void usage() {
       "    -p, --prefix <prefix>                      File prefix name.  THe output will end with '_<sample_name>_counts.csv'\n"
       "    -s, --sample-barcodes <sample_file>        Sample barcodes file\n"
       "    -t, --threads <threads>                    Number of threads (ignored: the GPU engine has no CPU workers)\n"
+      "        --strand <forward|reverse|both>        Which orientation of a read is counted: as it stands, as its reverse complement,\n"
+      "                                               or as it stands first and reversed when the constant region mismatches (unaligned BAM\n"
+      "                                               from a basecaller, non-directional preps, an R2 file).  reverse and both print one\n"
+      "                                               further line, 'Reverse strand matches:' [default: forward]\n"
       "        --device <id>                          HIP device to run on [default: 0]\n"
       "        --gpus <n>                             Run on n GPUs: one process per GPU, reads sharded, one exchange at the end [default: 1]\n"
       "        --devices <a,b,..>                     The HIP device of each of the n ranks [default: 0,1,..]\n"
@@ -128,6 +132,10 @@ Args parse_args(int argc, char** argv) {
       char* end;
       a.min_quality = strtof(s.c_str(), &end);
       if (s.empty() || *end != 0) die("Unable to convert min score to a float");
+    } else if (k == "--strand") {
+      const std::string s = val();
+      if (s != "forward" && s != "reverse" && s != "both") die("--strand must be forward, reverse or both");
+      a.strand = s == "forward" ? BC_STRAND_FORWARD : (s == "reverse" ? BC_STRAND_REVERSE : BC_STRAND_BOTH);
     } else if (k == "--device") {
       a.device = parse_u16("device", val().c_str());
     } else if (k == "--gpus") {
@@ -291,6 +299,7 @@ void set_up_plan(Run& r) {
   }
   bc_plan_set_max_errors(r.plan, r.args.sample_errors, r.args.barcodes_errors, r.args.constant_errors);
   bc_plan_set_min_quality(r.plan, r.args.min_quality);
+  if (bc_plan_set_strand(r.plan, r.args.strand)) die("%s", bc_last_error());
   printf("%s\n\n", max_errors_display(r).c_str());  // main.rs:65
 
   r.engine = bc_engine_create(r.plan, r.args.device, nullptr, nullptr);
@@ -307,6 +316,7 @@ void count_reads(Run& r, bool multi, bool root, uint64_t* total_reads, uint64_t 
   if (!multi) {
     if (bc_fastq_count(r.engine, r.args.fastq.c_str(), total_reads, progress, nullptr)) die("Read Fastq error: %s", bc_last_error());
     if (bc_engine_counters(r.engine, counters)) die("%s", bc_last_error());
+    if (bc_engine_strand_reads(r.engine, nullptr, &r.reverse_matched)) die("%s", bc_last_error());
     return;
   }
   bc_comm* comm = make_comm(r.args);
@@ -314,6 +324,10 @@ void count_reads(Run& r, bool multi, bool root, uint64_t* total_reads, uint64_t 
                            root ? progress : nullptr, nullptr))
     die("Read Fastq error: %s", bc_last_error());
   if (bc_comm_sum_u64(comm, total_reads, 1, 0)) die("%s", bc_last_error());
+  if (r.args.strand != BC_STRAND_FORWARD) {  // (a collective of its own, so that a forward job exchanges what it always did)
+    if (bc_engine_strand_reads(r.engine, nullptr, &r.reverse_matched)) die("%s", bc_last_error());
+    if (bc_comm_sum_u64(comm, &r.reverse_matched, 1, 0)) die("%s", bc_last_error());
+  }
   if (bc_engine_finish_all(r.engine, comm, 0, counters, n_rows)) die("%s", bc_last_error());
   if (bc_comm_barrier(comm)) die("%s", bc_last_error());  // nobody leaves while a peer still reads its messages
   bc_comm_destroy(comm);
@@ -336,7 +350,7 @@ int main(int argc, char** argv) {
   count_reads(r, multi, root, &total_reads, counters, &n_rows);
   if (root) {
     printf("Total sequences:             %s\r\n", commas((uint32_t)total_reads).c_str());  // input.rs:85-87
-    printf("%s\n\n", errors_display(counters).c_str());                                      // main.rs:124
+    printf("%s%s\n\n", errors_display(counters).c_str(), strand_display(r).c_str());  // main.rs:124
     printf("Compute time: %s\n\n", elapsed_text(now_ms() - start_ms).c_str());              // main.rs:127-135
 
     printf("-WRITING COUNTS-\n");

@@ -124,6 +124,11 @@ std::string errors_display(const uint64_t c[BC_NCOUNTERS]) {  // info.rs:141-172
          "\nDuplicates:                  " + g(BC_DUPLICATES) + "\nLow quality barcodes:        " + g(BC_LOW_QUALITY);
 }
 
+std::string strand_display(const Run& r) {
+  if (r.args.strand == BC_STRAND_FORWARD) return "";
+  return "\nReverse strand matches:      " + commas(r.reverse_matched);
+}
+
 // ---- what the writers decide on ---------------------------------------------------------------------------------------
 
 // every sample key that exists before a row is seen (info.rs:698-719), the known sets, and the engine's index of each key
@@ -616,7 +621,7 @@ void write_stats_file(const Run& r, time_t start, double start_ms, const uint64_
        "\nBarcodes: " + (r.args.has_counted ? r.args.counted_barcodes : std::string("None")) + "\n\n";
   s += format_display(r) + "\n\n";
   s += max_errors_display(r) + "\n";
-  s += "-RESULTS-\nTotal sequences:             " + commas((uint32_t)total_reads) + "\n" + errors_display(counters) + "\n\n";
+  s += "-RESULTS-\nTotal sequences:             " + commas((uint32_t)total_reads) + "\n" + errors_display(counters) + strand_display(r) + "\n\n";
   s += "-OUTPUT FILES-\n";
   for (size_t i = 0; i < r.output_files.size() && i < r.output_counts.size(); ++i)
     s += "File & barcodes counted: " + r.output_files[i] + "\t" + commas(r.output_counts[i]) + "\n";

@@ -24,6 +24,7 @@ struct Args {  // arguments.rs:6-20; filled by parse_args (barcode_count_main.cp
   int barcodes_errors = -1, sample_errors = -1, constant_errors = -1;
   float min_quality = 0.0f;
   int device = 0;
+  int strand = BC_STRAND_FORWARD;  // --strand forward | reverse | both (bc_plan_set_strand)
   // several GPUs
   int gpus = 1;
   std::vector<int> devices;        // --devices a,b,..: the HIP device of each rank (default 0 .. gpus-1)
@@ -37,6 +38,7 @@ struct Run {
   bc_plan* plan = nullptr;
   bc_engine* engine = nullptr;
   uint32_t barcode_num = 0;
+  uint64_t reverse_matched = 0;  // --strand reverse | both: the job's reads that matched as their reverse complement
   std::vector<std::pair<std::string, std::string>> samples;               // (sequence, id) in index order
   std::vector<std::vector<std::pair<std::string, std::string>>> counted;  // per barcode position
   // Results (info.rs:661-665) rebuilt from the engine's rows: sample key -> (tuple of sequences -> count)
@@ -70,6 +72,8 @@ std::string elapsed_text(double ms_total);
 std::string format_display(const Run& r);
 std::string max_errors_display(const Run& r);
 std::string errors_display(const uint64_t counters[BC_NCOUNTERS]);
+// "" for --strand forward (stdout and the stats file stay byte for byte what they were), else one further line
+std::string strand_display(const Run& r);
 
 // Results as the writers see it: samples, counted, sample_keys, counted_map and sample_index from the plan
 void describe_results(Run& r);

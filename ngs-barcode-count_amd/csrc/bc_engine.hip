@@ -256,6 +256,7 @@ static void engine_free(bc_engine* e) {
   if (e->d_wide_keys) (void)hipFree(e->d_wide_keys);
   if (e->d_wide_cnts) (void)hipFree(e->d_wide_cnts);
   if (e->d_counters) (void)hipFree(e->d_counters);
+  strand_free(e);
   if (e->d_plan) (void)hipFree(e->d_plan);
   if (e->reset_stream) (void)hipStreamSynchronize(e->reset_stream);
   if (e->reset_fork) (void)hipEventDestroy(e->reset_fork);
@@ -397,6 +398,11 @@ static int engine_init(bc_engine* e, const bc_plan* p, int device_id, void* hip_
       e->allocs.push_back(d);
       G.dtable_a = (uint64_t)(uintptr_t)d;
     }
+  }
+  e->strand = p->strand;
+  if (const char* sc = getenv("BC_STRAND_CHUNK")) {
+    const uint64_t c = strtoull(sc, nullptr, 0) & ~255ull;
+    if (c) e->strand_chunk = std::min<uint64_t>(c, 1ull << 30);  // (select numbers a chunk's reads in 32 bits)
   }
   if (const char* cl = getenv("BC_COUNT_LOG")) e->count_log = strcmp(cl, "auto") == 0 ? 2 : atoi(cl);
   if (const char* ch = getenv("BC_COUNT_LOG_HOT")) e->log_hot = atoi(ch) != 0;
@@ -650,7 +656,8 @@ static uint32_t match_flags(const MatchShape& s, bool tables, bool hot) {
 // s: match_shape() of the batch; NW = s.generic_nw
 template <int NW, int NWW>
 static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
-                        uint32_t read_len, uint32_t nd, uint64_t n_reads, uint64_t trace_off, const MatchShape& s) {
+                        uint32_t read_len, uint32_t nd, uint64_t n_reads, uint8_t* trace_outcome, uint64_t* trace_idx,
+                        const MatchShape& s) {
   // log mode (bc_fold.h): the batch goes through in chunks of at most log_chunk reads, each matched into the log and
   // folded before the next one overwrites it.  (The same code object with the hot-counter cache on or off: the kernel
   // lays out its LDS from the flag, so a launch without the cache does not ask for its bytes.)
@@ -725,8 +732,8 @@ static int launch_match(bc_engine* e, const void* d_seq, const void* d_qual, con
     const uint8_t* a_qual = d_qual ? (const uint8_t*)d_qual + c0 * stride : nullptr;
     const uint16_t* a_lens = d_lens ? (const uint16_t*)d_lens + c0 : nullptr;
     const uint16_t* a_qlens = d_qlens ? (const uint16_t*)d_qlens + c0 : nullptr;
-    uint8_t* a_to = e->trace_outcome ? e->trace_outcome + trace_off + c0 : nullptr;
-    uint64_t* a_ti = e->trace_idx ? e->trace_idx + trace_off + c0 : nullptr;
+    uint8_t* a_to = trace_outcome ? trace_outcome + c0 : nullptr;
+    uint64_t* a_ti = trace_idx ? trace_idx + c0 : nullptr;
     uint32_t* a_log = use_log ? e->d_log : nullptr;
     uint64_t a_n = n_c, a_smask = slot_mask(e);
     uint32_t a_region = s.region;
@@ -798,7 +805,7 @@ static int ensure_long(bc_engine* e) {
 }
 
 static int launch_long(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens,
-                       uint32_t stride, uint32_t read_len, uint64_t n_reads, uint64_t trace_off) {
+                       uint32_t stride, uint32_t read_len, uint64_t n_reads, uint8_t* trace_outcome, uint64_t* trace_idx) {
   int rc = ensure_long(e);
   if (rc != BC_OK) return rc;
   if ((rc = settle_owed(e)) != BC_OK) return rc;
@@ -809,7 +816,7 @@ static int launch_long(bc_engine* e, const void* d_seq, const void* d_qual, cons
   hipLaunchKernelGGL(long_match_kernel, dim3((uint32_t)blocks), dim3(256), 0, e->stream, e->d_long, (const uint8_t*)d_seq,
                      (const uint8_t*)d_qual, (const uint16_t*)d_lens, (const uint16_t*)d_qlens, stride, read_len, n_reads,
                      e->d_table, e->d_slots, e->d_vals, e->d_ready, slot_mask(e), e->d_counters,
-                     e->trace_outcome ? e->trace_outcome + trace_off : nullptr, e->trace_idx ? e->trace_idx + trace_off : nullptr);
+                     trace_outcome, trace_idx);
   HIP_TRY(hipGetLastError());
   e->table_all_dirty = true;  // (this kernel adds to the table without flagging blocks)
   e->last_kernel = "long_match_kernel";
@@ -824,9 +831,8 @@ void bc::fix_error_launch(const DevGroup& G, uint32_t q1, uint32_t q2, uint32_t 
   hipLaunchKernelGGL(fix_error_kernel, dim3(1), dim3(64), 0, 0, G, q1, q2, qn, qx, d_out);
 }
 
-static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
-                              uint32_t read_len, uint64_t n_reads, uint64_t trace_off) {
-  if (n_reads == 0) return BC_OK;
+// what every submit checks first
+static int submit_check(const bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, uint32_t stride, uint32_t read_len) {
   if (!d_seq || stride == 0) {
     set_error("submit: null sequence buffer or zero stride");
     return BC_ERR_INVALID;
@@ -844,6 +850,12 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
     set_error("submit: read_len exceeds stride");
     return BC_ERR_INVALID;
   }
+  return BC_OK;
+}
+
+int bc::submit_forward(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
+                       uint32_t read_len, uint64_t n_reads, uint8_t* trace_outcome, uint64_t* trace_idx) {
+  const uint32_t maxlen = d_lens ? stride : read_len;
   const uint32_t nd = (maxlen + 3) / 4;
   HIP_TRY(hipSetDevice(e->device));
   e->table_materialized = false;
@@ -853,18 +865,18 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
     if (rc != BC_OK) return rc;
   }
   // plans or reads beyond the lane-per-read kernel's widths: the wave-per-read kernel (bc_long.h)
-  if (e->long_only || maxlen > 320u) return launch_long(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads, trace_off);
-  MatchShape s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr,
+  if (e->long_only || maxlen > 320u) return launch_long(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads, trace_outcome, trace_idx);
+  MatchShape s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, trace_outcome != nullptr,
                              e->lds_limit, e->pipe, e->qshare, e->lhash_mode);
   // With the quality filter on, the pipelined fetch keeps two tile regions per wave: from 315 bases on (four waves x
   // two regions of 64 x 315 bytes and their slack) they no longer fit the LDS.  Such a batch is fetched on demand
   // into one region per wave -- the path every partial tile takes -- instead of being refused.
   if (s.pipe && s.lds + 64 > e->lds_limit)
-    s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, e->trace_outcome != nullptr, e->lds_limit, false,
+    s = match_shape(e->h.plan, e->table_entries, stride, read_len, d_lens != nullptr, trace_outcome != nullptr, e->lds_limit, false,
                     e->qshare, e->lhash_mode);
   const int nww = s.jit.NWW;  // words of candidate offsets: the exact count; the instantiations round it up
 #define BC_LAUNCH(NW_, NWW_) \
-  return launch_match<NW_, NWW_>(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, nd, n_reads, trace_off, s)
+  return launch_match<NW_, NWW_>(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, nd, n_reads, trace_outcome, trace_idx, s)
   if (s.generic_nw == 4) {
     if (nww <= 1) BC_LAUNCH(4, 1);
     if (nww <= 2) BC_LAUNCH(4, 2);
@@ -878,6 +890,18 @@ static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qua
   if (nww <= 4) BC_LAUNCH(10, 4);  // (up to 320 bases: longer reads went to the wave-per-read kernel)
   BC_LAUNCH(10, 10);
 #undef BC_LAUNCH
+}
+
+// A plan's strand setting decides here, once, who counts the batch: as it stands (the engine's only path until a plan
+// asks otherwise), or through bc_strand.hip.
+static int submit_device_impl(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
+                              uint32_t read_len, uint64_t n_reads, uint64_t trace_off) {
+  if (n_reads == 0) return BC_OK;
+  const int rc = submit_check(e, d_seq, d_qual, d_lens, stride, read_len);
+  if (rc != BC_OK) return rc;
+  if (e->strand != BC_STRAND_FORWARD) return submit_strand(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads, trace_off);
+  return submit_forward(e, d_seq, d_qual, d_lens, d_qlens, stride, read_len, n_reads,
+                        e->trace_outcome ? e->trace_outcome + trace_off : nullptr, e->trace_idx ? e->trace_idx + trace_off : nullptr);
 }
 
 extern "C" {

@@ -206,6 +206,14 @@ struct bc_engine {
   uint64_t wide_n = 0;
   uint64_t wide_sorts = 0;               // sorts made since the engine was created (bc_engine_wide_render_sorts)
   float wide_sort_ms = 0.f;              // export + order keys + sort + gather of the last one, from HIP events
+  // The strand setting (bc_strand.hip), read from the plan at creation.  BC_STRAND_FORWARD: nothing below is ever
+  // allocated and no submit goes near it.
+  int strand = BC_STRAND_FORWARD;
+  uint64_t strand_chunk = 1ull << 24;    // reads per orient / two-pass round (BC_STRAND_CHUNK, a multiple of 256)
+  uint8_t* d_strand = nullptr;           // the scratch batch, the list, select's block counts and the outcome bytes
+  size_t strand_bytes = 0;
+  unsigned long long* d_strand_stats = nullptr;  // retried | matched_reverse | BC_MATCHED ahead of the reverse pass
+  uint32_t* strand_count_pin = nullptr;  // pinned: the number of reads select has listed
 };
 
 namespace bc {
@@ -225,6 +233,18 @@ int settle_owed(bc_engine* e);
 void fix_error_launch(const DevGroup& G, uint32_t q1, uint32_t q2, uint32_t qn, uint32_t qx, uint32_t* d_out);
 // staging copy pageable <-> pinned, cut into slices for a few threads (BC_STAGE_THREADS)
 void staged_copy(void* dst, const void* src, size_t n);
+// One checked batch counted as it stands, enqueued on the engine's stream: what every submit of a BC_STRAND_FORWARD
+// engine is, and each pass of the others.  trace_outcome / trace_idx: where the per-read outcomes and indexes go
+// (both NULL: not recorded).
+int submit_forward(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
+                   uint32_t read_len, uint64_t n_reads, uint8_t* trace_outcome, uint64_t* trace_idx);
+
+// ---- defined in bc_strand.hip ----
+// A checked batch of an engine whose strand is not BC_STRAND_FORWARD; a caller's trace receives the reads' final
+// outcomes from trace_off on.  BC_STRAND_BOTH: waits for the device once per chunk of strand_chunk reads.
+int submit_strand(bc_engine* e, const void* d_seq, const void* d_qual, const void* d_lens, const void* d_qlens, uint32_t stride,
+                  uint32_t read_len, uint64_t n_reads, uint64_t trace_off);
+void strand_free(bc_engine* e);  // (the stream has drained)
 
 // ---- defined in bc_keys.hip ----
 // Keeps the key table at most half full for `more` further keys (plans with a random barcode or raw captures; a no-op

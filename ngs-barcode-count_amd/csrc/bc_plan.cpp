@@ -1043,6 +1043,15 @@ int bc_plan_set_min_quality(bc_plan* p, float q) {
   return BC_OK;
 }
 uint32_t bc_plan_quality_threshold(const bc_plan* p, uint32_t run_len) { return p->quality_threshold(run_len); }
+int bc_plan_set_strand(bc_plan* p, int strand) {
+  if (strand != BC_STRAND_FORWARD && strand != BC_STRAND_REVERSE && strand != BC_STRAND_BOTH) {
+    bc::set_error("bc_plan_set_strand: the strand is BC_STRAND_FORWARD, BC_STRAND_REVERSE or BC_STRAND_BOTH");
+    return BC_ERR_INVALID;
+  }
+  p->strand = strand;
+  return BC_OK;
+}
+int bc_plan_strand(const bc_plan* p) { return p->strand; }
 
 uint64_t bc_plan_table_entries(const bc_plan* p) {
   bc::HostDevPlan h;

@@ -115,6 +115,7 @@ struct bc_plan {
   uint16_t max_constant = 0, max_sample = 0;
   std::vector<uint16_t> max_barcode;
   float min_quality = 0.0f;
+  int strand = 0;  // BC_STRAND_*: which orientation of a read is counted (bc_plan_set_strand; an engine reads it at creation)
 
   void recompute_budgets();
   // lowers to the device form; false + set_error() when the engine cannot run the plan.  allow_wide: a plan whose
