@@ -248,13 +248,10 @@ static void engine_free(bc_engine* e) {
   if (e->d_slots) (void)hipFree(e->d_slots);
   if (e->d_vals) (void)hipFree(e->d_vals);
   if (e->d_ready) (void)hipFree(e->d_ready);
-  if (e->d_sums) (void)hipFree(e->d_sums);
-  if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
-  for (void* p : e->d_re)
-    if (p) (void)hipFree(p);
-  if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
-  if (e->d_wide_keys) (void)hipFree(e->d_wide_keys);
-  if (e->d_wide_cnts) (void)hipFree(e->d_wide_cnts);
+  e->sums.drop();
+  e->raw_rows.drop();
+  e->wide_rows.drop();
+  for (RawEnrichSegs& r : e->raw_enrich) r.drop();
   if (e->d_counters) (void)hipFree(e->d_counters);
   strand_free(e);
   if (e->d_plan) (void)hipFree(e->d_plan);

@@ -1,6 +1,7 @@
 // bc_engine_impl.h -- what the engine's translation units (bc_engine.hip, bc_keys.hip, bc_finish.hip, bc_probe.hip,
-// bc_synth.hip, bc_text.hip) share: struct bc_engine, the HIP_TRY / ScratchGuard pair every function of the C ABI is
-// written with, the functions one of them defines and another calls, and the undocumented hooks of the exchange
+// bc_synth.hip, bc_text.hip) share: struct bc_engine and the small structs that own what the text renderers keep on the
+// device between calls, the HIP_TRY / ScratchGuard pair every function of the C ABI is written with (and StreamTimer
+// beside them), the functions one of them defines and another calls, and the undocumented hooks of the exchange
 // (bc_comm.hip includes it for those alone).  A kernel is launched only from the file that defines it: what crosses a
 // file is a host function declared here.  Internal: no other file includes it.
 #ifndef BC_ENGINE_IMPL_H
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -58,6 +60,100 @@ struct ScratchGuard {
     const hipError_t rc = hipEventCreateWithFlags(out, hipEventDisableTiming);
     if (rc == hipSuccess) events.push_back(*out);
     return rc;
+  }
+  // p, a dmalloc of this guard (or NULL), is the caller's from now on
+  template <typename T>
+  T* release(T* p) {
+    if (p) dev.erase(std::find(dev.begin(), dev.end(), (void*)p));
+    return p;
+  }
+};
+
+// The device time a stream spends between start() and stop(), from two events that a guard owns.
+struct StreamTimer {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipStream_t stream = nullptr;
+  hipError_t start(ScratchGuard& g, hipStream_t s) {
+    stream = s;
+    for (hipEvent_t* ev : {&ev0, &ev1}) {
+      const hipError_t rc = hipEventCreate(ev);
+      if (rc != hipSuccess) return rc;
+      g.events.push_back(*ev);
+    }
+    return hipEventRecord(ev0, stream);
+  }
+  // waits for the stream; *ms is written only when everything before it went well
+  hipError_t stop(float* ms) {
+    hipError_t rc = hipEventRecord(ev1, stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
+    if (rc == hipSuccess) (void)hipEventElapsedTime(ms, ev0, ev1);
+    return rc;
+  }
+};
+
+// ---- what the text renderers (bc_text.hip) keep on the device between calls ----
+// counts_epoch of the engine moves whenever what bc_engine_finish would hand out may have changed (counts_changed());
+// a result derived from the counts carries the epoch it was made for, is served only while the two agree, and is dropped
+// and rebuilt by the next render after that.  An epoch of 0 never agrees.
+
+// The IDs of the counted sets (bc_line.h), built at the first render, and the canonical map of the enrichment renderers
+// beside it.  Both live among the engine's allocs and go with the engine: there is nothing to drop.
+struct LabelPool {
+  bool ready = false;
+  uint32_t* d_off = nullptr;             // per group N_g + 1 offsets, back to back
+  uint8_t* d_bytes = nullptr;
+  uint32_t off_start[bc::kMaxGroups] = {0};
+  uint32_t max_len[bc::kMaxGroups] = {0};  // the longest ID of each counted set
+  bool canon_ready = false;              // the canonical map has been built
+  uint32_t* d_canon = nullptr;           // canon[off_g + i]; NULL when no set shares an ID
+};
+
+// The folded marginal sums of a dense plan (bc_enrich_render.h): S * SUM singles, then S * P doubles.  Never served for
+// a table somebody else may write (caller-owned, or its pointer handed out): their epoch stays 0 then.
+struct DenseSums {
+  uint64_t epoch = 0;
+  unsigned long long* d = nullptr;
+  uint64_t passes = 0;                   // table passes made for them since the engine was created
+  void drop() {
+    if (d) (void)hipFree(d);
+    d = nullptr;
+    epoch = 0;
+  }
+};
+
+// The keys and counts of a sparse plan in the order of its files: the raw-key renderer's (key, count) pairs, re-keyed
+// and sorted (bc_raw_render.h, bc_sort.h), or the wide-key renderer's keys of key_words u64 each, gathered into order
+// (bc_wide_render.h).  The S + 1 renders of one merged run sort once.
+struct SortedRows {
+  uint64_t epoch = 0;
+  uint64_t* d_keys = nullptr;
+  uint32_t* d_cnts = nullptr;
+  uint64_t n = 0;
+  uint64_t sorts = 0;                    // sorts made since the engine was created
+  float sort_ms = 0.f;                   // export + (re-key | order keys) + sort (+ gather) of the last one, from HIP events
+  void drop() {
+    if (d_keys) (void)hipFree(d_keys);
+    if (d_cnts) (void)hipFree(d_cnts);
+    d_keys = nullptr;
+    d_cnts = nullptr;
+    n = 0;
+    epoch = 0;
+  }
+};
+
+// One kind of a raw-key plan's enrichment (bc_raw_enrich_render.h): the (projected key, sum) segments made from the
+// sorted rows (project, bc_sort.h, bc_reduce.h), in one allocation -- n keys, n sums, n_seg + 1 segment starts, u64 all.
+struct RawEnrichSegs {
+  uint64_t epoch = 0;
+  void* d = nullptr;
+  uint64_t n = 0;
+  uint32_t n_seg = 0;
+  void drop() {
+    if (d) (void)hipFree(d);
+    d = nullptr;
+    n = 0;
+    n_seg = 0;
+    epoch = 0;
   }
 };
 
@@ -163,49 +259,16 @@ struct bc_engine {
   bc::LongHost lh;
   bc::LongPlan* d_long = nullptr;
   const bc_plan* src_plan = nullptr;  // (the caller keeps the plan alive for the engine's lifetime)
-  // the label pool of the text renderer (bc_render.h), built at the first render: the IDs of the counted sets
-  bool render_pool_ready = false;
-  uint32_t* d_label_off = nullptr;
-  uint8_t* d_label_bytes = nullptr;
-  uint32_t label_off_start[bc::kMaxGroups] = {0};
-  uint32_t label_max[bc::kMaxGroups] = {0};  // the longest ID of each counted set
   bool table_materialized = false;  // random-barcode plans: d_table holds the per-tuple distinct counts of the current
                                     // key set (bc_engine_materialize_table), possibly summed over ranks since
-  // The enrichment renderer (bc_enrich_render.h).  counts_epoch moves whenever what bc_engine_finish would hand out may
-  // have changed (counts_changed()); the folded sums on the device are those of epoch sums_epoch and are served only
-  // while the two agree -- and never for a table somebody else may write (caller-owned, or its pointer handed out).
-  uint64_t counts_epoch = 1, sums_epoch = 0;
-  unsigned long long* d_sums = nullptr;  // S * SUM singles, then S * P doubles
-  uint64_t sums_passes = 0;              // table passes made for them since the engine was created
-  bool canon_ready = false;              // the canonical maps of the label pool have been built
-  uint32_t* d_canon = nullptr;           // canon[off_g + i]; NULL when no set shares an ID
-  // The raw-key renderer (bc_raw_render.h): the map's (key, count) pairs, re-keyed and sorted (bc_sort.h), kept on the
-  // device for the counts of epoch raw_epoch -- the S + 1 renders of one merged run sort once.  Whatever moves
-  // counts_epoch (submits, imports, resets, clear_keys, finish_all) retires them; the next render frees and rebuilds.
-  uint64_t raw_epoch = 0;
-  uint64_t* d_raw_keys = nullptr;
-  uint32_t* d_raw_cnts = nullptr;
-  uint64_t raw_n = 0;
-  uint64_t raw_sorts = 0;                // sorts made since the engine was created (bc_engine_raw_render_sorts)
-  float raw_sort_ms = 0.f;               // export + re-key + sort of the last one, from HIP events
-  // The raw-key enrichment renderer (bc_raw_enrich_render.h): per kind ([0] Single, [1] Double) the (projected key, sum)
-  // segments made from the sorted pairs above (project, bc_sort.h, bc_reduce.h), in one allocation -- re_n keys, re_n
-  // sums, re_segs + 1 segment starts, u64 all -- built at the kind's first render of a counts epoch and retired with the
-  // sorted pairs.
-  uint64_t re_epoch[2] = {0, 0};
-  void* d_re[2] = {nullptr, nullptr};
-  uint64_t re_n[2] = {0, 0};
-  uint32_t re_segs[2] = {0, 0};
+  // what the text renderers keep between calls (the structs above)
+  uint64_t counts_epoch = 1;
+  LabelPool labels;
+  DenseSums sums;
+  SortedRows raw_rows, wide_rows;
+  RawEnrichSegs raw_enrich[2];           // [0] Single, [1] Double: made from raw_rows, and dropped with them
   uint64_t raw_enrich_builds = 0;        // kinds built since the engine was created (bc_engine_raw_enrich_reduces)
   float raw_enrich_ms = 0.f;             // project + sort + reduce of the last one, from HIP events
-  // The wide-key renderer (bc_wide_render.h): the exported keys (key_words u64 each) and counts gathered into the order
-  // of the files, kept on the device under the counts epoch exactly as d_raw_keys is.
-  uint64_t wide_epoch = 0;
-  uint64_t* d_wide_keys = nullptr;
-  uint32_t* d_wide_cnts = nullptr;
-  uint64_t wide_n = 0;
-  uint64_t wide_sorts = 0;               // sorts made since the engine was created (bc_engine_wide_render_sorts)
-  float wide_sort_ms = 0.f;              // export + order keys + sort + gather of the last one, from HIP events
   // The strand setting (bc_strand.hip), read from the plan at creation.  BC_STRAND_FORWARD: nothing below is ever
   // allocated and no submit goes near it.
   int strand = BC_STRAND_FORWARD;

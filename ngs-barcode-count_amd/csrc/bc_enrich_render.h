@@ -10,7 +10,7 @@
 // and to an ordered list of sample columns.  It has G fields joined by commas -- field g holds id_g (and field h id_h),
 // every other field is empty, as add_single / add_double build the key (info.rs:840-904) -- then one count per column:
 //     ,id,,c_0,c_1,..\n        c_m = sums[cols[m] * K + k], a u64 in decimal
-// and exists when some c_m is not zero.  IDs are copied verbatim from the label pool (bc_render.h).
+// and exists when some c_m is not zero.  IDs are copied verbatim from the label pool (bc_line.h).
 //
 // Entries of one known set whose IDs are byte-equal are ONE key of the reference's maps (they are keyed by text): the
 // sums are folded before any line is written -- enrich_fold_target names, for every key, the key of the smallest indices
@@ -18,11 +18,11 @@
 // Text that coincides ACROSS groups or pairs (possible only when some ID is empty: ",," is the empty ID of every group)
 // is NOT merged: such plans are not for this renderer.
 //
-// Nothing here indexes a local array: a line is measured and written from its END backwards, digit by digit.
+// A line is measured and written from its END backwards, digit by digit (bc_line.h).
 #ifndef BC_ENRICH_RENDER_H
 #define BC_ENRICH_RENDER_H
 
-#include "bc_render.h"
+#include "bc_line.h"
 
 namespace bc {
 
@@ -32,7 +32,7 @@ struct EnrichRenderView {
   const unsigned long long* sums;  // this kind's sums, folded: entry s * K + k
   const uint32_t* cols;            // sample index of every column
   const uint32_t* canon;           // canon[off_g + i]: the smallest index of set g with i's ID; NULL: no set shares an ID
-  const uint32_t* label_off;       // the label pool (bc_render.h)
+  const uint32_t* label_off;       // the label pool (bc_line.h)
   const uint8_t* label_bytes;
   uint64_t K;                      // keys per sample: SUM or P
   uint32_t n_cols;
@@ -46,27 +46,6 @@ struct EnrichKey {
   uint32_t g, h;  // the fields that hold an ID (h = g for a single)
   uint32_t i, j;  // indices into sets g and h
 };
-
-// x / 10 by multiplication: the high half of x * ceil(2^67 / 10), shifted by 3 -- exact for every u64
-BC_HD uint64_t enrich_div10(uint64_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __umul64hi(x, 0xCCCCCCCCCCCCCCCDull) >> 3;
-#else
-  return (uint64_t)(((unsigned __int128)x * 0xCCCCCCCCCCCCCCCDull) >> 64) >> 3;
-#endif
-}
-
-// decimal digits of x: 1 .. 20
-BC_HD uint32_t enrich_digits(uint64_t x) {
-  if ((x >> 32) == 0) return render_digits((uint32_t)x);
-  uint32_t d = 10;
-  uint64_t p = 10000000000ull;  // 10^d
-  while (d < 19 && x >= p) {
-    p *= 10u;
-    ++d;
-  }
-  return d + (x >= p);  // (at d = 19 p = 10^19 still fits; 10^20 does not)
-}
 
 // key -> the fields and indices it stands for (k < v.K)
 BC_HD EnrichKey enrich_key(const EnrichRenderView& v, uint64_t k) {
@@ -84,7 +63,7 @@ BC_HD EnrichKey enrich_key(const EnrichRenderView& v, uint64_t k) {
       if (k < sz || (g + 2 == v.G)) {  // (the last pair takes what is left)
         key.g = g;
         key.h = h;
-        key.j = render_take_digit(k, v.n[h]);
+        key.j = (uint32_t)take_digit(k, v.n[h]);
         key.i = (uint32_t)k;
         return key;
       }
@@ -114,11 +93,6 @@ BC_HD uint64_t enrich_fold_target(const EnrichRenderView& v, uint64_t k) {
 
 BC_HD uint64_t enrich_sum(const EnrichRenderView& v, uint32_t c, uint64_t k) { return v.sums[(uint64_t)v.cols[c] * v.K + k]; }
 
-BC_HD uint32_t enrich_label_len(const EnrichRenderView& v, uint32_t g, uint32_t i) {
-  const uint32_t* o = v.label_off + v.off_start[g] + i;
-  return o[1] - o[0];
-}
-
 // bytes of key k's line, '\n' included; 0 when every column is zero (no line)
 BC_HD uint32_t enrich_row_len(const EnrichRenderView& v, uint64_t k) {
   uint64_t any = 0;
@@ -126,51 +100,34 @@ BC_HD uint32_t enrich_row_len(const EnrichRenderView& v, uint64_t k) {
   for (uint32_t c = 0; c < v.n_cols; ++c) {
     const uint64_t x = enrich_sum(v, c, k);
     any |= x;
-    len += 1u + enrich_digits(x);  // ",count"
+    len += 1u + digits_u64(x);  // ",count"
   }
   if (!any) return 0;
   const EnrichKey key = enrich_key(v, k);
-  len += enrich_label_len(v, key.g, key.i);
-  if (v.kind == kEnrichDouble) len += enrich_label_len(v, key.h, key.j);
+  len += label_len(v.label_off, v.off_start[key.g], key.i);
+  if (v.kind == kEnrichDouble) len += label_len(v.label_off, v.off_start[key.h], key.j);
   return len;
 }
 
-// Writes the part of key k's line (len = enrich_row_len, not 0) that falls into the window dst[0 .. win): the line starts
-// at window position `at`, which may be negative or beyond the window (as render_row_write).
+// Writes the part of key k's line (len = enrich_row_len, not 0) that falls into the window dst[0 .. win); the line starts
+// at window position `at` (bc_line.h).
 template <typename Byte>
 BC_HD void enrich_row_write(const EnrichRenderView& v, uint64_t k, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
-  int64_t p = at + (int64_t)len;  // one past the byte written next (the line is written backwards)
-#define BC_ENRICH_PUT(ch)                                 \
-  do {                                                    \
-    --p;                                                  \
-    if (p >= 0 && p < (int64_t)win) dst[p] = (Byte)(ch);  \
-  } while (0)
-  BC_ENRICH_PUT('\n');
-  for (uint32_t c = v.n_cols; c-- > 0;) {
-    uint64_t x = enrich_sum(v, c, k);
-    do {
-      const uint64_t q = enrich_div10(x);
-      BC_ENRICH_PUT('0' + (uint32_t)(x - q * 10u));
-      x = q;
-    } while (x);
-    BC_ENRICH_PUT(',');
+  LineCursor<Byte> c(dst, at, len, win);
+  c.put('\n');
+  for (uint32_t m = v.n_cols; m-- > 0;) {
+    c.put_u64(enrich_sum(v, m, k));
+    c.put(',');
   }
   const EnrichKey key = enrich_key(v, k);
   for (uint32_t f = v.G; f-- > 0;) {
     // (for a single h == g: the first test takes it)
     if (f == key.h || f == key.g) {
       const uint32_t* o = v.label_off + v.off_start[f] + (f == key.h ? key.j : key.i);
-      const uint32_t a = o[0], n = o[1] - o[0];
-      // the label lies at [p - n, p): only its bytes inside the window are touched
-      int64_t lo = p - (int64_t)n, hi = p;
-      p = lo;
-      if (lo < 0) lo = 0;
-      if (hi > (int64_t)win) hi = (int64_t)win;
-      for (int64_t w = lo; w < hi; ++w) dst[w] = (Byte)v.label_bytes[a + (uint32_t)(w - p)];
+      c.put_label(v.label_bytes, o[0], o[1] - o[0]);
     }
-    if (f) BC_ENRICH_PUT(',');
+    if (f) c.put(',');
   }
-#undef BC_ENRICH_PUT
 }
 
 // the names bc_text_kernels.h reaches a view's lane code by

@@ -37,12 +37,11 @@
 //     ACGTACGT,,TTGCAAGC,3\n    Double of (0,2)
 // Lines come in ascending position: Single by (g, digit), Double by (pair, d_g, d_h).
 //
-// As in bc_render.h a line is measured and written from its END backwards, so no digit is ever kept in a local array.
+// A line is measured and written from its END backwards (bc_line.h).
 #ifndef BC_RAW_ENRICH_RENDER_H
 #define BC_RAW_ENRICH_RENDER_H
 
-#include "bc_enrich_render.h"
-#include "bc_raw_render.h"
+#include "bc_enrich_render.h"  // kEnrichSingle / kEnrichDouble
 
 namespace bc {
 
@@ -61,10 +60,10 @@ struct RawEnrichProj {
 // key = T * S + s  ->  the projected key
 BC_HD uint64_t raw_enrich_project(const RawEnrichProj& p, uint64_t key) {
   uint64_t r = key;
-  const uint64_t s = raw_take_digit(r, p.S);
+  const uint64_t s = take_digit(r, p.S);
   uint64_t dg = 0, dh = 0;
   for (uint32_t f = p.G; f-- > 0;) {  // (the digits come off innermost group first; only two of them are kept)
-    uint64_t d = raw_take_digit(r, p.radix[f]);
+    uint64_t d = take_digit(r, p.radix[f]);
     if (f != p.g && f != p.h) continue;
     if (p.canon && p.known[f]) d = p.canon[p.canon_off[f] + (uint32_t)d];
     if (f == p.h) dh = d;
@@ -133,7 +132,7 @@ BC_HD RawEnrichLine raw_enrich_line(const RawEnrichView& v, uint64_t i) {
     L.h = g + 1u + left;
   }
   uint64_t r = v.keys[i];
-  L.s = (uint32_t)raw_take_digit(r, v.S);
+  L.s = (uint32_t)take_digit(r, v.S);
   L.D = r;
   return L;
 }
@@ -143,14 +142,7 @@ BC_HD RawEnrichLine raw_enrich_line(const RawEnrichView& v, uint64_t i) {
 BC_HD uint64_t raw_enrich_run_sum(const RawEnrichView& v, const RawEnrichLine& L, uint64_t i, uint32_t s) {
   const uint64_t want = L.D * v.S + s;
   const uint64_t end = i + v.S < L.hi ? i + v.S : L.hi;
-  uint64_t lo = i, hi = end;  // [lo, hi)
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (v.keys[mid] < want)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
+  const uint64_t lo = key_lower_bound(v.keys, i, end, want);
   return lo < end && v.keys[lo] == want ? v.sums[lo] : 0ull;
 }
 
@@ -159,7 +151,7 @@ BC_HD bool raw_enrich_has_line(const RawEnrichView& v, const RawEnrichLine& L, u
   if (!v.merged) return L.s == v.sample;
   if (i == L.lo) return true;
   uint64_t p = v.keys[i - 1];
-  (void)raw_take_digit(p, v.S);
+  (void)take_digit(p, v.S);
   return p != L.D;
 }
 
@@ -169,9 +161,7 @@ BC_HD uint64_t raw_enrich_col_sum(const RawEnrichView& v, const RawEnrichLine& L
 
 // bytes of the text of group f's digit d
 BC_HD uint32_t raw_enrich_field_len(const RawEnrichView& v, uint32_t f, uint64_t d) {
-  if (v.raw_len[f]) return v.raw_len[f];
-  const uint32_t* o = v.label_off + v.off_start[f] + (uint32_t)d;
-  return o[1] - o[0];
+  return v.raw_len[f] ? v.raw_len[f] : label_len(v.label_off, v.off_start[f], (uint32_t)d);
 }
 
 // bytes of position i's line, '\n' included; 0: no line
@@ -183,70 +173,38 @@ BC_HD uint32_t raw_enrich_row_len(const RawEnrichView& v, uint64_t i) {
   for (uint32_t c = 0; c < v.n_cols; ++c) {
     const uint64_t x = raw_enrich_col_sum(v, L, i, c);
     any |= x;
-    len += 1u + enrich_digits(x);  // ",count"
+    len += 1u + digits_u64(x);  // ",count"
   }
   if (v.merged && !any) return 0;
   uint64_t r = L.D;
-  if (L.h != L.g) len += raw_enrich_field_len(v, L.h, raw_take_digit(r, v.radix[L.h]));
+  if (L.h != L.g) len += raw_enrich_field_len(v, L.h, take_digit(r, v.radix[L.h]));
   return len + raw_enrich_field_len(v, L.g, r);
 }
 
 // Writes the part of position i's line (len = raw_enrich_row_len, not 0) that falls into the window dst[0 .. win); the
-// line starts at window position `at`, which may be negative or beyond the window (render_row_write's contract).
+// line starts at window position `at` (bc_line.h).
 template <typename Byte>
 BC_HD void raw_enrich_row_write(const RawEnrichView& v, uint64_t i, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
   const RawEnrichLine L = raw_enrich_line(v, i);
-  int64_t p = at + (int64_t)len;  // one past the byte written next (the line is written backwards)
-#define BC_RAW_ENRICH_PUT(ch)                             \
-  do {                                                    \
-    --p;                                                  \
-    if (p >= 0 && p < (int64_t)win) dst[p] = (Byte)(ch);  \
-  } while (0)
-  BC_RAW_ENRICH_PUT('\n');
-  for (uint32_t c = v.n_cols; c-- > 0;) {
-    uint64_t x = raw_enrich_col_sum(v, L, i, c);
-    do {
-      const uint64_t q = enrich_div10(x);
-      BC_RAW_ENRICH_PUT('0' + (uint32_t)(x - q * 10u));
-      x = q;
-    } while (x);
-    BC_RAW_ENRICH_PUT(',');
+  LineCursor<Byte> c(dst, at, len, win);
+  c.put('\n');
+  for (uint32_t m = v.n_cols; m-- > 0;) {
+    c.put_u64(raw_enrich_col_sum(v, L, i, m));
+    c.put(',');
   }
   uint64_t r = L.D;
   for (uint32_t f = v.G; f-- > 0;) {
     if (f == L.h || f == L.g) {  // (h comes first, and takes its digit off: what is left is g's)
-      uint64_t d = f == L.g ? r : raw_take_digit(r, v.radix[f]);
+      const uint64_t d = f == L.g ? r : take_digit(r, v.radix[f]);
       if (v.raw_len[f]) {
-        // the capture lies at [p - n, p): base k at p - n + k, and the code gives up base 0 first
-        const uint32_t n = v.raw_len[f];
-        p -= (int64_t)n;
-        for (uint32_t k = 0; k < n; ++k) {
-          uint32_t c5;
-          if ((d >> 32) == 0) {
-            const uint32_t d32 = (uint32_t)d, q = d32 / 5u;
-            c5 = d32 - q * 5u;
-            d = q;
-          } else {
-            const uint64_t q = d / 5u;
-            c5 = (uint32_t)(d - q * 5u);
-            d = q;
-          }
-          const int64_t w = p + (int64_t)k;
-          if (w >= 0 && w < (int64_t)win) dst[w] = (Byte)raw_base_char(c5);
-        }
+        c.put_bases(d, v.raw_len[f]);
       } else {
         const uint32_t* o = v.label_off + v.off_start[f] + (uint32_t)d;
-        const uint32_t a = o[0], n = o[1] - o[0];
-        int64_t lo = p - (int64_t)n, hi = p;
-        p = lo;
-        if (lo < 0) lo = 0;
-        if (hi > (int64_t)win) hi = (int64_t)win;
-        for (int64_t w = lo; w < hi; ++w) dst[w] = (Byte)v.label_bytes[a + (uint32_t)(w - p)];
+        c.put_label(v.label_bytes, o[0], o[1] - o[0]);
       }
     }
-    if (f) BC_RAW_ENRICH_PUT(',');
+    if (f) c.put(',');
   }
-#undef BC_RAW_ENRICH_PUT
 }
 
 // the names bc_text_kernels.h reaches a view's lane code by

@@ -22,16 +22,16 @@
 //                       ascending in s) and some listed sample counts; the lane looks its columns up in the run
 // and the line is
 //     f_0,f_1,..,f_{G-1},c_0,c_1,..\n
-// f_g: the ID of the set's entry, copied from the label pool (bc_render.h's) when group g is a known set, else the
+// f_g: the ID of the set's entry, copied from the label pool (bc_line.h) when group g is a known set, else the
 // capture's bases "ACTGN"[c_k], first base first;  c_k: the count of the column in decimal ("0" for a sample that does
 // not count the tuple; a sample may be listed twice, the list may be in any order).
 //
-// As in bc_render.h a line is measured and written from its END backwards, so no digit is ever kept in a local array;
-// inside a raw field the bases come out in ascending k, which is the order the code gives them up.
+// A line is measured and written from its END backwards (bc_line.h); inside a raw field the bases come out in
+// ascending k, which is the order the code gives them up.
 #ifndef BC_RAW_RENDER_H
 #define BC_RAW_RENDER_H
 
-#include "bc_render.h"
+#include "bc_line.h"
 
 namespace bc {
 
@@ -52,46 +52,23 @@ struct RawRenderView {
   uint64_t radix[kRenderMaxG];      // the set's size, or 5^raw_len
 };
 
-// r -> its least significant digit of the given radix; r loses it
-BC_HD uint64_t raw_take_digit(uint64_t& r, uint64_t radix) {
-  if (((r | radix) >> 32) == 0) {
-    const uint32_t r32 = (uint32_t)r, n32 = (uint32_t)radix, q = r32 / n32;
-    r = q;
-    return r32 - q * n32;
-  }
-  const uint64_t q = r / radix;
-  const uint64_t d = r - q * radix;
-  r = q;
-  return d;
-}
-
-// "ACTGN"[d] without a table in memory
-BC_HD uint32_t raw_base_char(uint32_t d) { return (uint32_t)((0x4E47544341ull >> (8u * d)) & 0xFFu); }
-
 // the count of sample `s` for the tuple whose run starts at position i (0: the sample does not count it).  The run is
 // the at most S entries from i on with the same T, ascending in s: a binary search for T * S + s among them.
 BC_HD uint32_t raw_run_count(const RawRenderView& v, uint64_t i, uint64_t T, uint32_t s) {
   const uint64_t want = T * v.S + s;
-  uint64_t lo = i, hi = i + v.S < v.n ? i + v.S : v.n;  // [lo, hi)
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (v.keys[mid] < want)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
+  const uint64_t lo = key_lower_bound(v.keys, i, i + v.S < v.n ? i + v.S : v.n, want);
   return lo < v.n && lo < i + v.S && v.keys[lo] == want ? v.cnts[lo] : 0u;
 }
 
 // Position i -> does it have a line at all, and its tuple number T.  (The count columns follow from raw_col_count.)
 BC_HD bool raw_has_line(const RawRenderView& v, uint64_t i, uint64_t& T) {
   uint64_t r = v.keys[i];
-  const uint32_t s = (uint32_t)raw_take_digit(r, v.S);
+  const uint32_t s = (uint32_t)take_digit(r, v.S);
   T = r;
   if (!v.merged) return s == v.sample;
   if (i == 0) return true;
   uint64_t p = v.keys[i - 1];
-  (void)raw_take_digit(p, v.S);
+  (void)take_digit(p, v.S);
   return p != T;
 }
 
@@ -108,77 +85,40 @@ BC_HD uint32_t raw_row_len(const RawRenderView& v, uint64_t i) {
   for (uint32_t c = 0; c < v.n_cols; ++c) {
     const uint32_t x = raw_col_count(v, i, T, c);
     any |= x;
-    len += 1u + render_digits(x);  // ",count"
+    len += 1u + digits_u32(x);  // ",count"
   }
   if (v.merged && !any) return 0;
   uint64_t r = T;
   for (uint32_t g = v.G; g-- > 0;) {
-    const uint64_t d = raw_take_digit(r, v.radix[g]);
-    if (v.raw_len[g]) {
-      len += v.raw_len[g];
-    } else {
-      const uint32_t* o = v.label_off + v.off_start[g] + (uint32_t)d;
-      len += o[1] - o[0];
-    }
+    const uint64_t d = take_digit(r, v.radix[g]);
+    len += v.raw_len[g] ? v.raw_len[g] : label_len(v.label_off, v.off_start[g], (uint32_t)d);
   }
   return len;
 }
 
 // Writes the part of position i's line (len = raw_row_len, not 0) that falls into the window dst[0 .. win); the line
-// starts at window position `at`, which may be negative or beyond the window (render_row_write's contract).
+// starts at window position `at` (bc_line.h).
 template <typename Byte>
 BC_HD void raw_row_write(const RawRenderView& v, uint64_t i, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
   uint64_t T;
   (void)raw_has_line(v, i, T);
-  int64_t p = at + (int64_t)len;  // one past the byte written next (the line is written backwards)
-#define BC_RAW_PUT(ch)                                    \
-  do {                                                    \
-    --p;                                                  \
-    if (p >= 0 && p < (int64_t)win) dst[p] = (Byte)(ch);  \
-  } while (0)
-  BC_RAW_PUT('\n');
-  for (uint32_t c = v.n_cols; c-- > 0;) {
-    uint32_t x = raw_col_count(v, i, T, c);
-    do {
-      const uint32_t q = x / 10u;  // (a multiplication: the divisor is a constant)
-      BC_RAW_PUT('0' + (x - q * 10u));
-      x = q;
-    } while (x);
-    BC_RAW_PUT(',');
+  LineCursor<Byte> c(dst, at, len, win);
+  c.put('\n');
+  for (uint32_t k = v.n_cols; k-- > 0;) {
+    c.put_u32(raw_col_count(v, i, T, k));
+    c.put(',');
   }
   uint64_t r = T;
   for (uint32_t g = v.G; g-- > 0;) {
-    uint64_t d = raw_take_digit(r, v.radix[g]);
+    const uint64_t d = take_digit(r, v.radix[g]);
     if (v.raw_len[g]) {
-      // the capture lies at [p - len, p): base k at p - len + k, and the code gives up base 0 first
-      const uint32_t n = v.raw_len[g];
-      p -= (int64_t)n;
-      for (uint32_t k = 0; k < n; ++k) {
-        uint32_t c5;
-        if ((d >> 32) == 0) {
-          const uint32_t d32 = (uint32_t)d, q = d32 / 5u;
-          c5 = d32 - q * 5u;
-          d = q;
-        } else {
-          const uint64_t q = d / 5u;
-          c5 = (uint32_t)(d - q * 5u);
-          d = q;
-        }
-        const int64_t w = p + (int64_t)k;
-        if (w >= 0 && w < (int64_t)win) dst[w] = (Byte)raw_base_char(c5);
-      }
+      c.put_bases(d, v.raw_len[g]);
     } else {
       const uint32_t* o = v.label_off + v.off_start[g] + (uint32_t)d;
-      const uint32_t a = o[0], n = o[1] - o[0];
-      int64_t lo = p - (int64_t)n, hi = p;
-      p = lo;
-      if (lo < 0) lo = 0;
-      if (hi > (int64_t)win) hi = (int64_t)win;
-      for (int64_t w = lo; w < hi; ++w) dst[w] = (Byte)v.label_bytes[a + (uint32_t)(w - p)];
+      c.put_label(v.label_bytes, o[0], o[1] - o[0]);
     }
-    if (g) BC_RAW_PUT(',');
+    if (g) c.put(',');
   }
-#undef BC_RAW_PUT
 }
 
 // the names bc_text_kernels.h reaches a view's lane code by

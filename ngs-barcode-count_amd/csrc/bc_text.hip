@@ -1,11 +1,14 @@
-// bc_text.hip -- the output files written as CSV text on the device: the counts files of a dense plan
-// (bc_engine_render_counts / _merged; lane code bc_render.h), the Single and Double enrichment files
-// (bc_engine_render_enriched / _merged; bc_enrich_render.h) and the sorted counts files of a raw-key plan
-// (bc_engine_render_raw_counts / _merged; bc_raw_render.h, bc_sort.h) and of a wide-key plan
-// (bc_engine_render_wide_counts / _merged; bc_wide_render.h, bc_sort.h), and the Single and Double files of a raw-key
-// plan (bc_engine_render_raw_enriched / _merged; bc_raw_enrich_render.h, bc_sort.h, bc_reduce.h).  A renderer is a view
-// struct with lane code and a front end that checks the request and fills the view; the kernels (bc_text_kernels.h) and the host loop around them
-// (stream_text) are templates over the view.
+// bc_text.hip -- the output files written as CSV text on the device, five renderers:
+//   counts of a dense plan        bc_engine_render_counts / _merged            bc_render.h
+//   counts of a raw-key plan      bc_engine_render_raw_counts / _merged        bc_raw_render.h, bc_sort.h
+//   counts of a wide-key plan     bc_engine_render_wide_counts / _merged       bc_wide_render.h, bc_sort.h
+//   Single / Double, dense plan   bc_engine_render_enriched / _merged          bc_enrich_render.h
+//   Single / Double, raw-key plan bc_engine_render_raw_enriched / _merged      bc_raw_enrich_render.h, bc_sort.h, bc_reduce.h
+// A renderer is a view struct with lane code (written with bc_line.h) and a front end here that checks the request,
+// has what the view reads made or served from the engine (the structs of bc_engine_impl.h, kept under the counts
+// epoch) and fills the view.  What the front ends share comes first: the label pool, the host loop around the kernels
+// of bc_text_kernels.h (stream_text; both templates over the view), the refusals, the description of a sparse plan's
+// counted groups, the longest line, and the closing call (render_lines).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -20,6 +23,7 @@
 #include "bc_raw_enrich_render.h"
 #include "bc_raw_render.h"
 #include "bc_reduce.h"
+#include "bc_render.h"
 #include "bc_sort.h"
 #include "bc_text_kernels.h"
 #include "bc_wide_render.h"
@@ -30,14 +34,14 @@ using namespace bc;
 
 // The IDs of the counted sets on the device, once per engine: per group N_g + 1 offsets, and the bytes back to back.
 static int ensure_render_pool(bc_engine* e, const char* who) {
-  if (e->render_pool_ready) return BC_OK;
+  if (e->labels.ready) return BC_OK;
   const uint32_t G = e->barcode_num;
   std::vector<uint32_t> off;
   std::string bytes;
   try {
     for (uint32_t g = 0; g < G; ++g) {
-      e->label_off_start[g] = (uint32_t)off.size();
-      e->label_max[g] = 0;
+      e->labels.off_start[g] = (uint32_t)off.size();
+      e->labels.max_len[g] = 0;
       const uint32_t n = bc_plan_n_counted(e->src_plan, g);
       for (uint32_t i = 0; i < n; ++i) {
         const char* id = bc_plan_counted_id(e->src_plan, g, i);
@@ -48,7 +52,7 @@ static int ensure_render_pool(bc_engine* e, const char* who) {
         }
         off.push_back((uint32_t)bytes.size());
         if (len) bytes.append(id, len);
-        e->label_max[g] = std::max<uint32_t>(e->label_max[g], (uint32_t)len);
+        e->labels.max_len[g] = std::max<uint32_t>(e->labels.max_len[g], (uint32_t)len);
       }
       off.push_back((uint32_t)bytes.size());
     }
@@ -83,9 +87,9 @@ static int ensure_render_pool(bc_engine* e, const char* who) {
     set_error(std::string(who) + ": out of host memory");
     return BC_ERR_NOMEM;
   }
-  e->d_label_off = (uint32_t*)d_pool;
-  e->d_label_bytes = (uint8_t*)d_pool + off_bytes;
-  e->render_pool_ready = true;
+  e->labels.d_off = (uint32_t*)d_pool;
+  e->labels.d_bytes = (uint8_t*)d_pool + off_bytes;
+  e->labels.ready = true;
   return BC_OK;
 }
 
@@ -251,18 +255,147 @@ static int upload_cols(bc_engine* e, ScratchGuard& g, const uint32_t* cols, uint
   return BC_OK;
 }
 
+// What a front end renders, for the refusals below.  (The dense enrichment refuses through enrich_shape.)
+enum TextFamily { kDenseCounts, kRawCounts, kWideCounts, kRawEnrich };
+
+// The engine's plan is one of: dense; sparse with one-word keys (raw); sparse with wider keys (wide); and a sparse plan
+// may keep its sample barcode raw, which no renderer takes.  BC_OK when `fam` renders that, else its refusal.
+static int check_plan_shape(const bc_engine* e, const char* who, TextFamily fam) {
+  const DevPlan& P = e->h.plan;
+  const bool enrich = fam == kRawEnrich;
+  std::string why;
+  if (fam == kDenseCounts) {
+    if (P.sparse)
+      why = "the plan keeps raw captures, whose rows are sequences, not indices: write them from bc_engine_row_text on the host";
+  } else if (!P.sparse) {
+    why = enrich ? "the plan has a dense table: its Single / Double files come from bc_engine_render_enriched / "
+                   "bc_engine_render_enriched_merged"
+                 : "the plan has a dense table: its files come from bc_engine_render_counts / bc_engine_render_merged";
+  } else if (fam != kWideCounts && e->key_words > 1) {
+    why = "the plan's keys are " + std::to_string(e->key_words) + " words wide; " +
+          (enrich ? "build its Single / Double files" : "write its rows") + " from bc_engine_finish + bc_engine_row_text on the host";
+  } else if (e->has_sample_group && P.groups[0].mode == kSetNone) {
+    why = std::string("the sample barcode is kept raw, so a sample is a capture, not an index: ") +
+          (enrich ? "build the Single / Double files" : "write the rows") + " from bc_engine_finish + bc_engine_row_text on the host";
+  } else if (fam == kWideCounts && e->key_words <= 1) {
+    why = "the plan's keys are one word wide: its files come from bc_engine_render_raw_counts / bc_engine_render_raw_merged";
+  }
+  if (why.empty()) return BC_OK;
+  set_error(std::string(who) + ": " + why);
+  return BC_ERR_UNSUPPORTED;
+}
+
+static int check_kind(const char* who, int kind) {
+  if (kind == BC_ENRICH_SINGLE || kind == BC_ENRICH_DOUBLE) return BC_OK;
+  set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
+  return BC_ERR_INVALID;
+}
+
+// counted set g still has the n entries the table's axes / the key's digits were made for (it cannot be otherwise)
+static int check_set_size(const bc_engine* e, const char* who, uint32_t g, uint32_t n) {
+  if (bc_plan_n_counted(e->src_plan, g) == n) return BC_OK;
+  set_error(std::string(who) + ": the plan's sets changed after the engine was created");
+  return BC_ERR_STATE;
+}
+
+// The counted groups of a sparse plan, as its views read them.  The caller gives G and, per group, raw_len (bases of a
+// raw capture; 0: a known set) and n_ids (the set's size); describe_groups adds the rest once the label pool is ready.
+struct CountedGroups {
+  uint32_t G;
+  uint32_t raw_len[bc::kRenderMaxG];
+  uint32_t n_ids[bc::kRenderMaxG];
+  uint32_t off_start[bc::kRenderMaxG];  // known set: where its offsets start in the label pool
+  uint32_t longest[bc::kRenderMaxG];    // bytes of the group's longest field
+  uint64_t radix[bc::kRenderMaxG];      // the set's size, or 5^raw_len (past 27 bases it wraps: wide keys have no radix)
+};
+
+static int describe_groups(const bc_engine* e, const char* who, CountedGroups& cg) {
+  for (uint32_t g = 0; g < cg.G; ++g) {
+    cg.off_start[g] = 0;
+    if (cg.raw_len[g]) {
+      cg.longest[g] = cg.raw_len[g];
+      cg.radix[g] = 1;
+      for (uint32_t k = 0; k < cg.raw_len[g]; ++k) cg.radix[g] *= 5;
+      continue;
+    }
+    const int rc = check_set_size(e, who, g, cg.n_ids[g]);
+    if (rc != BC_OK) return rc;
+    cg.radix[g] = cg.n_ids[g];
+    cg.off_start[g] = e->labels.off_start[g];
+    cg.longest[g] = e->labels.max_len[g];
+  }
+  return BC_OK;
+}
+
+// a one-word sparse plan's counted groups (they follow the sample group, when there is one): G, raw_len, n_ids
+static int raw_plan_groups(const bc_engine* e, const char* who, CountedGroups& cg) {
+  const DevPlan& P = e->h.plan;
+  const uint32_t g0 = e->has_sample_group ? 1u : 0u;
+  memset(&cg, 0, sizeof cg);
+  cg.G = e->barcode_num;
+  if (cg.G > (uint32_t)bc::kRenderMaxG || g0 + cg.G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
+    set_error(std::string(who) + ": the plan's groups do not fit the view");
+    return BC_ERR_STATE;
+  }
+  for (uint32_t g = 0; g < cg.G; ++g) {
+    const DevGroup& Gr = P.groups[g0 + g];
+    if (Gr.mode == kSetNone)
+      cg.raw_len[g] = Gr.len;
+    else
+      cg.n_ids[g] = Gr.n_refs;
+  }
+  return BC_OK;
+}
+
+// the longest a counts line can be: every group's longest field, the commas, '\n', and ",4294967295" per column
+static uint64_t counts_max_line(uint32_t G, const uint32_t* longest, uint32_t n_cols) {
+  uint64_t max_line = 1 + (G ? G - 1 : 0) + 11ull * n_cols;
+  for (uint32_t g = 0; g < G; ++g) max_line += longest[g];
+  return max_line;
+}
+
+// ... and a Single (Double) line: the longest field (the two longest of different groups), G - 1 commas, '\n', and a
+// comma and 20 digits per column
+static uint64_t enrich_max_line(uint32_t G, const uint32_t* longest, uint32_t n_cols, int kind) {
+  uint32_t top[2] = {0, 0};
+  for (uint32_t g = 0; g < G; ++g) {
+    const uint32_t m = longest[g];
+    if (m > top[0]) {
+      top[1] = top[0];
+      top[0] = m;
+    } else if (m > top[1]) {
+      top[1] = m;
+    }
+  }
+  return 1 + (G - 1) + 21ull * n_cols + top[0] + (kind == BC_ENRICH_DOUBLE ? top[1] : 0u);
+}
+
+// How every front end ends, its view filled but for the columns and the label pool (which is ready): the lines of the
+// keys that have one go to `fn` (stream_text).
+template <class View>
+static int render_lines(bc_engine* e, const char* who, View& v, uint64_t max_line, const uint32_t* cols, uint32_t n_cols,
+                        bc_text_fn fn, void* user, uint64_t* n_rows) {
+  int rc = check_max_line(who, max_line);
+  if (rc != BC_OK) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  ScratchGuard g;
+  uint32_t* d_cols = nullptr;
+  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
+  v.cols = d_cols;
+  v.n_cols = n_cols;
+  v.label_off = e->labels.d_off;
+  v.label_bytes = e->labels.d_bytes;
+  return stream_text(e, who, v, max_line, fn, user, n_rows);
+}
+
 // ---- counts of a dense plan as text (bc_render.h) ----
 
 // The lines of the tuples for which some listed sample counts, in ascending tuple order (stream_text).
 static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn, void* user,
                        uint64_t* n_rows) {
   if (n_rows) *n_rows = 0;
-  const DevPlan& P = e->h.plan;
-  if (P.sparse) {
-    set_error(std::string(who) + ": the plan keeps raw captures, whose rows are sequences, not indices: write them from "
-              "bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
+  int rc = check_plan_shape(e, who, kDenseCounts);
+  if (rc) return rc;
   static_assert(bc::kRenderMaxG >= kMaxGroups, "a plan's counted barcodes fit the view");
   bc::RenderView v;
   memset(&v, 0, sizeof v);
@@ -270,37 +403,21 @@ static int render_text(bc_engine* e, const char* who, const uint32_t* cols, uint
   v.T = 1;
   const uint32_t g0 = e->has_sample_group ? 1u : 0u;
   for (uint32_t g = 0; g < v.G; ++g) {
-    v.n[g] = P.groups[g0 + g].n_refs;
+    v.n[g] = e->h.plan.groups[g0 + g].n_refs;
     v.T *= v.n[g];
   }
   const uint64_t S = v.T ? e->table_entries / v.T : 0;
-  int rc = check_request(who, cols, n_cols, fn, S);
-  if (rc) return rc;
+  if ((rc = check_request(who, cols, n_cols, fn, S)) != BC_OK) return rc;
   if ((rc = dense_counts_ready(e)) != BC_OK) return rc;
   if (n_cols == 0 || v.T == 0 || e->table_entries == 0) return BC_OK;
   if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
   for (uint32_t g = 0; g < v.G; ++g) {
-    if (bc_plan_n_counted(e->src_plan, g) != v.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
-      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-      return BC_ERR_STATE;
-    }
-    v.off_start[g] = e->label_off_start[g];
-    max_line += e->label_max[g];
+    if ((rc = check_set_size(e, who, g, v.n[g])) != BC_OK) return rc;
+    v.off_start[g] = e->labels.off_start[g];
   }
-  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
-  HIP_TRY(hipSetDevice(e->device));
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
   v.table = e->d_table;
   v.bits = e->bits_dirty ? e->d_bits : nullptr;  // two-level counting, not folded: read as they stand
-  v.cols = d_cols;
-  v.n_cols = n_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
+  return render_lines(e, who, v, counts_max_line(v.G, e->labels.max_len, n_cols), cols, n_cols, fn, user, n_rows);
 }
 
 extern "C" {
@@ -342,44 +459,27 @@ static hipError_t raw_rekey_launch(uint64_t* d_keys, uint64_t n, uint64_t t_spac
   return hipGetLastError();
 }
 
-// the sums of one kind of a raw-key plan's enrichment (k = 0: Single, 1: Double; ensure_raw_enrich below)
-static void raw_enrich_drop(bc_engine* e, int k) {
-  if (e->d_re[k]) (void)hipFree(e->d_re[k]);
-  e->d_re[k] = nullptr;
-  e->re_n[k] = 0;
-  e->re_segs[k] = 0;
-  e->re_epoch[k] = 0;
-}
-
+// (the enrichment segments are made from the sorted rows: they go together)
 static void raw_sorted_drop(bc_engine* e) {
-  raw_enrich_drop(e, 0);  // (made from the sorted pairs: they go together)
-  raw_enrich_drop(e, 1);
-  if (e->d_raw_keys) (void)hipFree(e->d_raw_keys);
-  if (e->d_raw_cnts) (void)hipFree(e->d_raw_cnts);
-  e->d_raw_keys = nullptr;
-  e->d_raw_cnts = nullptr;
-  e->raw_n = 0;
-  e->raw_epoch = 0;
+  for (RawEnrichSegs& r : e->raw_enrich) r.drop();
+  e->raw_rows.drop();
 }
 
-// The pairs of the current counts, sorted into the order of the files, in e->d_raw_keys / d_raw_cnts (raw_n of them):
-// served as they are while the counts epoch stands, else exported from the map (export_pairs, as finish_sparse does),
-// re-keyed and sorted.  Device memory while it runs:
-// the map's export bound x 12 bytes (kept), the same again for the sort's other buffers and n / 2 bytes of histograms.
+// The pairs of the current counts, sorted into the order of the files, in e->raw_rows: served as they are while the
+// counts epoch stands, else exported from the map (export_pairs, as finish_sparse does), re-keyed and sorted.  Device
+// memory while it runs: the map's export bound x 12 bytes (kept), the same again for the sort's other buffers and n / 2
+// bytes of histograms.
 static int ensure_raw_sorted(bc_engine* e, uint64_t t_space, uint32_t S) {
-  if (e->raw_epoch == e->counts_epoch) return BC_OK;
+  SortedRows& R = e->raw_rows;
+  if (R.epoch == e->counts_epoch) return BC_OK;
   raw_sorted_drop(e);
   if (!e->d_slots) {  // nothing was ever submitted or imported
-    e->raw_epoch = e->counts_epoch;
+    R.epoch = e->counts_epoch;
     return BC_OK;
   }
   ScratchGuard g;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIP_TRY(hipEventCreate(&ev0));
-  g.events.push_back(ev0);
-  HIP_TRY(hipEventCreate(&ev1));
-  g.events.push_back(ev1);
-  HIP_TRY(hipEventRecord(ev0, e->stream));
+  StreamTimer timer;
+  HIP_TRY(timer.start(g, e->stream));
   uint64_t* d_key = nullptr;
   uint32_t* d_cnt = nullptr;
   uint64_t n = 0;
@@ -401,87 +501,46 @@ static int ensure_raw_sorted(bc_engine* e, uint64_t t_space, uint32_t S) {
     }
     HIP_TRY(src);
   }
-  HIP_TRY(hipEventRecord(ev1, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipEventElapsedTime(&e->raw_sort_ms, ev0, ev1);
-  for (void* keep : {(void*)d_key, (void*)d_cnt}) g.dev.erase(std::find(g.dev.begin(), g.dev.end(), keep));
-  e->d_raw_keys = d_key;
-  e->d_raw_cnts = d_cnt;
-  e->raw_n = n;
-  e->raw_epoch = e->counts_epoch;
-  ++e->raw_sorts;
+  HIP_TRY(timer.stop(&R.sort_ms));
+  R.d_keys = g.release(d_key);
+  R.d_cnts = g.release(d_cnt);
+  R.n = n;
+  R.epoch = e->counts_epoch;
+  ++R.sorts;
   return BC_OK;
 }
 
 static int render_raw(bc_engine* e, const char* who, bool merged, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
                       void* user, uint64_t* n_rows) {
   if (n_rows) *n_rows = 0;
+  int rc = check_plan_shape(e, who, kRawCounts);
+  if (rc) return rc;
   const DevPlan& P = e->h.plan;
-  if (!P.sparse) {
-    set_error(std::string(who) + ": the plan has a dense table: its files come from bc_engine_render_counts / "
-              "bc_engine_render_merged");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->key_words > 1) {
-    set_error(std::string(who) + ": the plan's keys are " + std::to_string(e->key_words) +
-              " words wide; write its rows from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
-    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: write the rows "
-              "from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
   const uint32_t g0 = e->has_sample_group ? 1u : 0u;
   const uint32_t S = g0 ? P.groups[0].n_refs : 1u;
   const uint64_t t_space = g0 ? P.groups[0].table_stride : e->h.table_entries;
-  int rc = check_request(who, cols, n_cols, fn, S);
-  if (rc) return rc;
-  bc::RawRenderView v;
-  memset(&v, 0, sizeof v);
-  v.G = e->barcode_num;
-  v.S = S;
-  v.merged = merged ? 1u : 0u;
-  v.sample = n_cols ? cols[0] : 0u;
-  v.n_cols = n_cols;
-  if (v.G > (uint32_t)bc::kRenderMaxG || g0 + v.G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
-    set_error(std::string(who) + ": the plan's groups do not fit the view");
-    return BC_ERR_STATE;
-  }
+  if ((rc = check_request(who, cols, n_cols, fn, S)) != BC_OK) return rc;
+  CountedGroups cg;
+  if ((rc = raw_plan_groups(e, who, cg)) != BC_OK) return rc;
   HIP_TRY(hipSetDevice(e->device));
   if ((rc = bc_engine_sync(e)) != BC_OK) return rc;  // the submits, as bc_engine_finish waits for them
   if ((rc = ensure_raw_sorted(e, t_space, S)) != BC_OK) return rc;
-  if (n_cols == 0 || e->raw_n == 0) return BC_OK;
+  if (n_cols == 0 || e->raw_rows.n == 0) return BC_OK;
   if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    const DevGroup& G = P.groups[g0 + g];
-    if (G.mode == kSetNone) {
-      v.raw_len[g] = G.len;
-      v.radix[g] = 1;
-      for (uint32_t k = 0; k < G.len; ++k) v.radix[g] *= 5;
-      max_line += G.len;
-    } else {
-      if (bc_plan_n_counted(e->src_plan, g) != G.n_refs) {  // (cannot happen: the key's digits are the plan's sets)
-        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-        return BC_ERR_STATE;
-      }
-      v.radix[g] = G.n_refs;
-      v.off_start[g] = e->label_off_start[g];
-      max_line += e->label_max[g];
-    }
-  }
-  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
-  v.keys = e->d_raw_keys;
-  v.cnts = e->d_raw_cnts;
-  v.n = e->raw_n;
-  v.cols = d_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
+  if ((rc = describe_groups(e, who, cg)) != BC_OK) return rc;
+  bc::RawRenderView v;
+  memset(&v, 0, sizeof v);
+  v.G = cg.G;
+  v.S = S;
+  v.merged = merged ? 1u : 0u;
+  v.sample = cols[0];
+  memcpy(v.raw_len, cg.raw_len, sizeof v.raw_len);
+  memcpy(v.off_start, cg.off_start, sizeof v.off_start);
+  memcpy(v.radix, cg.radix, sizeof v.radix);
+  v.keys = e->raw_rows.d_keys;
+  v.cnts = e->raw_rows.d_cnts;
+  v.n = e->raw_rows.n;
+  return render_lines(e, who, v, counts_max_line(cg.G, cg.longest, n_cols), cols, n_cols, fn, user, n_rows);
 }
 
 extern "C" {
@@ -496,12 +555,12 @@ int bc_engine_render_raw_merged(bc_engine* e, const uint32_t* sample_idx, uint32
 }
 
 int bc_engine_raw_render_sorts(const bc_engine* e, uint64_t* n) {
-  *n = e->raw_sorts;
+  *n = e->raw_rows.sorts;
   return BC_OK;
 }
 
 int bc_engine_raw_render_sort_ms(const bc_engine* e, double* ms) {
-  *ms = (double)e->raw_sort_ms;
+  *ms = (double)e->raw_rows.sort_ms;
   return BC_OK;
 }
 
@@ -538,36 +597,23 @@ __global__ __launch_bounds__(256) void wide_gather_kernel(const unsigned long lo
 
 }  // namespace bc
 
-static void wide_sorted_drop(bc_engine* e) {
-  if (e->d_wide_keys) (void)hipFree(e->d_wide_keys);
-  if (e->d_wide_cnts) (void)hipFree(e->d_wide_cnts);
-  e->d_wide_keys = nullptr;
-  e->d_wide_cnts = nullptr;
-  e->wide_n = 0;
-  e->wide_epoch = 0;
-}
-
-// The keys and counts of the current counts in the order of the files, in e->d_wide_keys / d_wide_cnts (wide_n of them,
-// n x (W x 8 + 4) bytes): served as they are while the counts epoch stands, else exported from the map (export_wide, as
-// bc_engine_finish does), given order keys, sorted by them (bc::sort_words_launch) and gathered.  Peak device memory per
+// The keys and counts of the current counts in the order of the files, in e->wide_rows (n x (W x 8 + 4) bytes): served
+// as they are while the counts epoch stands, else exported from the map (export_wide, as bc_engine_finish does), given order keys, sorted by them (bc::sort_words_launch) and gathered.  Peak device memory per
 // exported row, beside the map: while the sort runs the exported row (W x 8 + 4), its order key (K x 8) and the sort's
 // 24.5 bytes -- (W + K) x 8 + 28.5; order keys and sort buffers are released before the gather, which holds the row
 // twice and the permutation -- 2 x (W x 8 + 4) + 4.  With K <= W - 1 <= 7 that is at most 148.5 bytes per row.  (A random-
 // barcode plan's export holds its table of tuples, slots x (W x 8 + 8) bytes, until the rows are out, before any of it.)
 static int ensure_wide_sorted(bc_engine* e, const bc::WideOrder& o) {
-  if (e->wide_epoch == e->counts_epoch) return BC_OK;
-  wide_sorted_drop(e);
+  SortedRows& R = e->wide_rows;
+  if (R.epoch == e->counts_epoch) return BC_OK;
+  R.drop();
   if (!e->d_slots) {  // nothing was ever submitted or imported
-    e->wide_epoch = e->counts_epoch;
+    R.epoch = e->counts_epoch;
     return BC_OK;
   }
   ScratchGuard g;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIP_TRY(hipEventCreate(&ev0));
-  g.events.push_back(ev0);
-  HIP_TRY(hipEventCreate(&ev1));
-  g.events.push_back(ev1);
-  HIP_TRY(hipEventRecord(ev0, e->stream));
+  StreamTimer timer;
+  HIP_TRY(timer.start(g, e->stream));
   unsigned long long* d_key = nullptr;
   uint32_t* d_cnt = nullptr;
   uint64_t n = 0;
@@ -604,53 +650,35 @@ static int ensure_wide_sorted(bc_engine* e, const bc::WideOrder& o) {
     hipLaunchKernelGGL(wide_gather_kernel, dim3(grid_for(n * W)), dim3(256), 0, e->stream, d_key, d_cnt, d_perm, n, W, d_key2, d_cnt2);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(ev1, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipEventElapsedTime(&e->wide_sort_ms, ev0, ev1);
-  for (void* keep : {(void*)d_key2, (void*)d_cnt2})
-    if (keep) g.dev.erase(std::find(g.dev.begin(), g.dev.end(), keep));
-  e->d_wide_keys = (uint64_t*)d_key2;
-  e->d_wide_cnts = d_cnt2;
-  e->wide_n = n;
-  e->wide_epoch = e->counts_epoch;
-  ++e->wide_sorts;
+  HIP_TRY(timer.stop(&R.sort_ms));
+  R.d_keys = (uint64_t*)g.release(d_key2);
+  R.d_cnts = g.release(d_cnt2);
+  R.n = n;
+  R.epoch = e->counts_epoch;
+  ++R.sorts;
   return BC_OK;
 }
 
 static int render_wide(bc_engine* e, const char* who, bool merged, const uint32_t* cols, uint32_t n_cols, bc_text_fn fn,
                        void* user, uint64_t* n_rows) {
   if (n_rows) *n_rows = 0;
-  const DevPlan& P = e->h.plan;
-  if (!P.sparse) {
-    set_error(std::string(who) + ": the plan has a dense table: its files come from bc_engine_render_counts / "
-              "bc_engine_render_merged");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
-    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: write the rows "
-              "from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->key_words <= 1) {
-    set_error(std::string(who) + ": the plan's keys are one word wide: its files come from bc_engine_render_raw_counts / "
-              "bc_engine_render_raw_merged");
-    return BC_ERR_UNSUPPORTED;
-  }
+  int rc = check_plan_shape(e, who, kWideCounts);
+  if (rc) return rc;
   const LongPlan& Q = e->lh.plan;  // (a wide-key plan is the wave-per-read kernel's: its groups hold the key layout)
   const uint32_t g0 = e->has_sample_group ? 1u : 0u;
   const uint32_t S = g0 ? Q.groups[0].n_refs : 1u;
-  int rc = check_request(who, cols, n_cols, fn, S);
-  if (rc) return rc;
+  if ((rc = check_request(who, cols, n_cols, fn, S)) != BC_OK) return rc;
   bc::WideRenderView v;
   bc::WideOrder o;
+  CountedGroups cg;
   memset(&v, 0, sizeof v);
   memset(&o, 0, sizeof o);
-  v.G = o.G = e->barcode_num;
+  memset(&cg, 0, sizeof cg);
+  v.G = o.G = cg.G = e->barcode_num;
   v.W = o.W = e->key_words;
   v.S = S;
   v.merged = merged ? 1u : 0u;
   v.sample = n_cols ? cols[0] : 0u;
-  v.n_cols = n_cols;
   // (cannot happen: a plan's groups fit the view, its sample group comes first and starts the payload)
   if (v.G > (uint32_t)bc::kRenderMaxG || g0 + v.G > Q.n_groups || v.W > (uint32_t)kMaxKeyWords ||
       (g0 && (Q.groups[0].type != kGroupSample || Q.groups[0].key_bit != 0))) {
@@ -664,9 +692,9 @@ static int render_wide(bc_engine* e, const char* who, bool merged, const uint32_
     const LongGroup& G = Q.groups[g0 + g];
     v.key_bit[g] = o.key_bit[g] = G.key_bit;
     if (G.n_refs == 0) {
-      v.raw_len[g] = o.raw_len[g] = G.len;
+      v.raw_len[g] = o.raw_len[g] = cg.raw_len[g] = G.len;
     } else {
-      v.n_ids[g] = G.n_refs;
+      v.n_ids[g] = cg.n_ids[g] = G.n_refs;
       o.obits[g] = bc::wide_bit_length(G.n_refs - 1u);
     }
     if (G.key_bit + (G.n_refs ? 32u : 3u * G.len) > pay_bits || (G.n_refs == 0 && G.len == 0)) {  // (cannot happen)
@@ -682,32 +710,14 @@ static int render_wide(bc_engine* e, const char* who, bool merged, const uint32_
   HIP_TRY(hipSetDevice(e->device));
   if ((rc = bc_engine_sync(e)) != BC_OK) return rc;  // the submits, as bc_engine_finish waits for them
   if ((rc = ensure_wide_sorted(e, o)) != BC_OK) return rc;
-  if (n_cols == 0 || e->wide_n == 0) return BC_OK;
+  if (n_cols == 0 || e->wide_rows.n == 0) return BC_OK;
   if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
-  uint64_t max_line = 1 + (v.G ? v.G - 1 : 0) + 11ull * n_cols;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    if (v.raw_len[g]) {
-      max_line += v.raw_len[g];
-    } else {
-      if (bc_plan_n_counted(e->src_plan, g) != v.n_ids[g]) {  // (cannot happen: the key's indices are the plan's sets)
-        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-        return BC_ERR_STATE;
-      }
-      v.off_start[g] = e->label_off_start[g];
-      max_line += e->label_max[g];
-    }
-  }
-  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
-  v.keys = e->d_wide_keys;
-  v.cnts = e->d_wide_cnts;
-  v.n = e->wide_n;
-  v.cols = d_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
+  if ((rc = describe_groups(e, who, cg)) != BC_OK) return rc;  // (a wide key has bit fields, not digits: no radix)
+  memcpy(v.off_start, cg.off_start, sizeof v.off_start);
+  v.keys = e->wide_rows.d_keys;
+  v.cnts = e->wide_rows.d_cnts;
+  v.n = e->wide_rows.n;
+  return render_lines(e, who, v, counts_max_line(cg.G, cg.longest, n_cols), cols, n_cols, fn, user, n_rows);
 }
 
 extern "C" {
@@ -722,12 +732,12 @@ int bc_engine_render_wide_merged(bc_engine* e, const uint32_t* sample_idx, uint3
 }
 
 int bc_engine_wide_render_sorts(const bc_engine* e, uint64_t* n) {
-  *n = e->wide_sorts;
+  *n = e->wide_rows.sorts;
   return BC_OK;
 }
 
 int bc_engine_wide_render_sort_ms(const bc_engine* e, double* ms) {
-  *ms = (double)e->wide_sort_ms;
+  *ms = (double)e->wide_rows.sort_ms;
   return BC_OK;
 }
 
@@ -767,7 +777,7 @@ static hipError_t enrich_fold_launch(const bc::EnrichRenderView& v, uint64_t n_s
 // For every counted set, which entries share an ID: canon[off_g + i] = the smallest index of set g whose ID equals i's.
 // Built once per engine, next to the label pool; uploaded only when some set does share an ID.
 static int ensure_canon(bc_engine* e, const char* who) {
-  if (e->canon_ready) return BC_OK;
+  if (e->labels.canon_ready) return BC_OK;
   std::vector<uint32_t> canon;
   bool shared = false;
   try {
@@ -789,26 +799,24 @@ static int ensure_canon(bc_engine* e, const char* who) {
     uint64_t d = 0;
     const int rc = upload(e, canon.data(), canon.size() * 4, &d);
     if (rc != BC_OK) return rc;
-    e->d_canon = (uint32_t*)(uintptr_t)d;
+    e->labels.d_canon = (uint32_t*)(uintptr_t)d;
   }
-  e->canon_ready = true;
+  e->labels.canon_ready = true;
   return BC_OK;
 }
 
-// the view of one kind over the engine's sums (cols / n_cols left to the caller)
+// the view of one kind over the engine's sums (columns and label pool: render_lines)
 static bc::EnrichRenderView enrich_view(const bc_engine* e, const EnrichShape& sh, uint64_t S, uint32_t kind) {
   bc::EnrichRenderView v;
   memset(&v, 0, sizeof v);
   v.kind = kind;
   v.G = sh.G;
   v.K = kind == bc::kEnrichSingle ? sh.sum_n : sh.pairs;
-  v.sums = e->d_sums + (kind == bc::kEnrichSingle ? 0 : S * sh.sum_n);
-  v.canon = e->d_canon;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
+  v.sums = e->sums.d + (kind == bc::kEnrichSingle ? 0 : S * sh.sum_n);
+  v.canon = e->labels.d_canon;
   for (uint32_t g = 0; g < sh.G; ++g) {
     v.n[g] = sh.n[g];
-    v.off_start[g] = e->label_off_start[g];
+    v.off_start[g] = e->labels.off_start[g];
   }
   return v;
 }
@@ -817,20 +825,20 @@ static bc::EnrichRenderView enrich_view(const bc_engine* e, const EnrichShape& s
 // the fold, then kept until the counts may have changed (counts_epoch).
 static int ensure_sums(bc_engine* e, const EnrichShape& sh, uint64_t S) {
   const bool keep = e->own_table && !e->table_exposed;  // (nobody else can write the table between two renders)
-  if (e->d_sums && keep && e->sums_epoch == e->counts_epoch) return BC_OK;
+  if (e->sums.d && keep && e->sums.epoch == e->counts_epoch) return BC_OK;
   HIP_TRY(hipSetDevice(e->device));
   const uint64_t n_single = S * sh.sum_n, n_double = S * sh.pairs;
-  e->sums_epoch = 0;
-  if (!e->d_sums) HIP_TRY(hipMalloc((void**)&e->d_sums, (size_t)(n_single + n_double) * 8));
-  HIP_TRY(hipMemsetAsync(e->d_sums, 0, (size_t)(n_single + n_double) * 8, e->stream));
-  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, e->d_sums,
-                           n_double ? e->d_sums + n_single : nullptr, e->stream));
-  if (e->d_canon) {
+  e->sums.epoch = 0;
+  if (!e->sums.d) HIP_TRY(hipMalloc((void**)&e->sums.d, (size_t)(n_single + n_double) * 8));
+  HIP_TRY(hipMemsetAsync(e->sums.d, 0, (size_t)(n_single + n_double) * 8, e->stream));
+  HIP_TRY(bc_enrich_launch(sh, e->d_table, e->bits_dirty ? e->d_bits : nullptr, e->table_entries, e->sums.d,
+                           n_double ? e->sums.d + n_single : nullptr, e->stream));
+  if (e->labels.d_canon) {
     HIP_TRY(enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichSingle), S, e->stream));
     if (n_double) HIP_TRY(enrich_fold_launch(enrich_view(e, sh, S, bc::kEnrichDouble), S, e->stream));
   }
-  ++e->sums_passes;
-  if (keep) e->sums_epoch = e->counts_epoch;
+  ++e->sums.passes;
+  if (keep) e->sums.epoch = e->counts_epoch;
   return BC_OK;
 }
 
@@ -840,41 +848,21 @@ static int render_enriched(bc_engine* e, const char* who, int kind, const uint32
   EnrichShape sh;
   uint64_t S = 0;
   if (!enrich_shape(e, who, &sh, &S)) return BC_ERR_UNSUPPORTED;
-  if (kind != BC_ENRICH_SINGLE && kind != BC_ENRICH_DOUBLE) {
-    set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
-    return BC_ERR_INVALID;
-  }
-  int rc = check_request(who, cols, n_cols, fn, S);
+  int rc = check_kind(who, kind);
   if (rc) return rc;
+  if ((rc = check_request(who, cols, n_cols, fn, S)) != BC_OK) return rc;
   if ((rc = dense_counts_ready(e)) != BC_OK) return rc;
   const uint64_t K = kind == BC_ENRICH_SINGLE ? sh.sum_n : sh.pairs;  // (no pairs below three counted barcodes)
   if (n_cols == 0 || K == 0 || e->table_entries == 0) return BC_OK;
   if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
   if ((rc = ensure_canon(e, who)) != BC_OK) return rc;
-  uint32_t longest[2] = {0, 0};  // the two longest IDs of different sets
-  for (uint32_t g = 0; g < sh.G; ++g) {
-    if (bc_plan_n_counted(e->src_plan, g) != sh.n[g]) {  // (cannot happen: the table's axes are the plan's sets)
-      set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-      return BC_ERR_STATE;
-    }
-    const uint32_t m = e->label_max[g];
-    if (m > longest[0]) {
-      longest[1] = longest[0];
-      longest[0] = m;
-    } else if (m > longest[1]) {
-      longest[1] = m;
-    }
-  }
-  const uint64_t max_line = 1 + (sh.G - 1) + 21ull * n_cols + longest[0] + (kind == BC_ENRICH_DOUBLE ? longest[1] : 0u);
-  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
+  for (uint32_t g = 0; g < sh.G; ++g)
+    if ((rc = check_set_size(e, who, g, sh.n[g])) != BC_OK) return rc;
+  const uint64_t max_line = enrich_max_line(sh.G, e->labels.max_len, n_cols, kind);
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;  // (before the table is passed over for a refused request)
   if ((rc = ensure_sums(e, sh, S)) != BC_OK) return rc;
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
   bc::EnrichRenderView v = enrich_view(e, sh, S, (uint32_t)kind);
-  v.cols = d_cols;
-  v.n_cols = n_cols;
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
+  return render_lines(e, who, v, max_line, cols, n_cols, fn, user, n_rows);
 }
 
 extern "C" {
@@ -889,7 +877,7 @@ int bc_engine_render_enriched_merged(bc_engine* e, int kind, const uint32_t* sam
 }
 
 int bc_engine_enrich_render_passes(const bc_engine* e, uint64_t* n) {
-  *n = e->sums_passes;
+  *n = e->sums.passes;
   return BC_OK;
 }
 
@@ -914,28 +902,25 @@ __global__ __launch_bounds__(256) void raw_enrich_project_kernel(RawEnrichProj p
 }  // namespace bc
 
 // The (projected key, sum) segments of one kind (k = 0: Single, 1: Double) for the sorted pairs as they stand
-// (ensure_raw_sorted has run, e->raw_n != 0), in e->d_re[k]: served as they are while the counts epoch stands, else
+// (ensure_raw_sorted has run, e->raw_rows.n != 0), in e->raw_enrich[k]: served as they are while the counts epoch stands, else
 // made projection by projection -- project, sort over the bits of the projection's bound, reduce the runs, keep the
 // runs in an allocation of their own size -- and joined at the end.  Every projection is sorted, the Single of group 0
 // too: its input ascends in d_0 already, but entries of one (d_0, s) are not adjacent there (s is the least significant
 // digit of every key in between), and a reduction needs them adjacent.
-// Device memory while a kind is built, n = raw_n: 12 n (projected pairs) + 12 n (the sort's other buffers, whose keys
+// Device memory while a kind is built, n = raw_rows.n: 12 n (projected pairs) + 12 n (the sort's other buffers, whose keys
 // then take the runs' keys) + n / 2 (histograms) + 8 n (sums) = 32.5 n bytes beside the kept 12 n -- one set of buffers,
 // allocated once and used by every projection in turn (the stream orders the reuse), released before the segments are
 // joined; kept: 16 bytes per (key, sample) with a sum, twice that while the segments are joined.
 static int ensure_raw_enrich(bc_engine* e, int k, const bc::RawEnrichProj& base) {
-  if (e->re_epoch[k] == e->counts_epoch) return BC_OK;
-  raw_enrich_drop(e, k);
-  const uint64_t n = e->raw_n;
+  RawEnrichSegs& R = e->raw_enrich[k];
+  if (R.epoch == e->counts_epoch) return BC_OK;
+  R.drop();
+  const uint64_t n = e->raw_rows.n;
   const uint32_t G = base.G, n_seg = k == 0 ? G : G * (G - 1u) / 2u;
   ScratchGuard segs;  // every projection's runs (keys, then sums) until they are joined
   std::vector<uint64_t> start;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIP_TRY(hipEventCreate(&ev0));
-  segs.events.push_back(ev0);
-  HIP_TRY(hipEventCreate(&ev1));
-  segs.events.push_back(ev1);
-  HIP_TRY(hipEventRecord(ev0, e->stream));
+  StreamTimer timer;
+  HIP_TRY(timer.start(segs, e->stream));
   try {
     start.reserve(n_seg + 1u);
     segs.dev.reserve(2u * n_seg + 2u);
@@ -965,7 +950,7 @@ static int ensure_raw_enrich(bc_engine* e, int k, const bc::RawEnrichProj& base)
         uint32_t key_bits = 1;
         while (key_bits < 64 && ((bound - 1u) >> key_bits) != 0) ++key_bits;
         hipLaunchKernelGGL(raw_enrich_project_kernel, dim3(grid_for(n)), dim3(256), 0, e->stream, p,
-                           (const unsigned long long*)e->d_raw_keys, (const uint32_t*)e->d_raw_cnts, n, (unsigned long long*)d_pk, d_pv);
+                           (const unsigned long long*)e->raw_rows.d_keys, (const uint32_t*)e->raw_rows.d_cnts, n, (unsigned long long*)d_pk, d_pv);
         HIP_TRY(hipGetLastError());
         HIP_TRY(bc::sort_pairs_launch(e->stream, d_pk, d_pv, d_tk, d_tv, n, key_bits, d_sort));
         HIP_TRY(bc::reduce_runs_launch(e->stream, d_pk, d_pv, n, d_tk, d_sum, d_runs, d_red));
@@ -1002,8 +987,7 @@ static int ensure_raw_enrich(bc_engine* e, int k, const bc::RawEnrichProj& base)
       HIP_TRY(hipMemcpyAsync(d_sums + start[q], segs.dev[2u * q + 1u], (size_t)len * 8, hipMemcpyDeviceToDevice, e->stream));
     }
     HIP_TRY(hipMemcpyAsync(d_sums + total, start.data(), (size_t)(n_seg + 1u) * 8, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipEventRecord(ev1, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(timer.stop(&e->raw_enrich_ms));
     return BC_OK;
   };
   const int rc = join();
@@ -1011,11 +995,10 @@ static int ensure_raw_enrich(bc_engine* e, int k, const bc::RawEnrichProj& base)
     (void)hipFree(d_all);
     return rc;
   }
-  (void)hipEventElapsedTime(&e->raw_enrich_ms, ev0, ev1);
-  e->d_re[k] = d_all;
-  e->re_n[k] = total;
-  e->re_segs[k] = n_seg;
-  e->re_epoch[k] = e->counts_epoch;
+  R.d = d_all;
+  R.n = total;
+  R.n_seg = n_seg;
+  R.epoch = e->counts_epoch;
   ++e->raw_enrich_builds;
   return BC_OK;
 }
@@ -1023,100 +1006,56 @@ static int ensure_raw_enrich(bc_engine* e, int k, const bc::RawEnrichProj& base)
 static int render_raw_enriched(bc_engine* e, const char* who, bool merged, int kind, const uint32_t* cols, uint32_t n_cols,
                                bc_text_fn fn, void* user, uint64_t* n_rows) {
   if (n_rows) *n_rows = 0;
+  int rc = check_plan_shape(e, who, kRawEnrich);
+  if (rc) return rc;
+  if ((rc = check_kind(who, kind)) != BC_OK) return rc;
   const DevPlan& P = e->h.plan;
-  if (!P.sparse) {
-    set_error(std::string(who) + ": the plan has a dense table: its Single / Double files come from "
-              "bc_engine_render_enriched / bc_engine_render_enriched_merged");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->key_words > 1) {
-    set_error(std::string(who) + ": the plan's keys are " + std::to_string(e->key_words) +
-              " words wide; build its Single / Double files from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (e->has_sample_group && P.groups[0].mode == kSetNone) {
-    set_error(std::string(who) + ": the sample barcode is kept raw, so a sample is a capture, not an index: build the "
-              "Single / Double files from bc_engine_finish + bc_engine_row_text on the host");
-    return BC_ERR_UNSUPPORTED;
-  }
-  if (kind != BC_ENRICH_SINGLE && kind != BC_ENRICH_DOUBLE) {
-    set_error(std::string(who) + ": kind " + std::to_string(kind) + " is neither BC_ENRICH_SINGLE nor BC_ENRICH_DOUBLE");
-    return BC_ERR_INVALID;
-  }
   const uint32_t g0 = e->has_sample_group ? 1u : 0u;
   const uint32_t S = g0 ? P.groups[0].n_refs : 1u;
   const uint64_t t_space = g0 ? P.groups[0].table_stride : e->h.table_entries;
-  int rc = check_request(who, cols, n_cols, fn, S);
-  if (rc) return rc;
-  const uint32_t G = e->barcode_num;
-  if (G > (uint32_t)bc::kRenderMaxG || g0 + G > P.n_groups) {  // (cannot happen: a plan's groups fit the view)
-    set_error(std::string(who) + ": the plan's groups do not fit the view");
-    return BC_ERR_STATE;
-  }
+  if ((rc = check_request(who, cols, n_cols, fn, S)) != BC_OK) return rc;
+  CountedGroups cg;
+  if ((rc = raw_plan_groups(e, who, cg)) != BC_OK) return rc;
+  const uint32_t G = cg.G;
   if (kind == BC_ENRICH_DOUBLE && G < 3) return BC_OK;  // (no pairs below three counted barcodes, as the dense call)
   HIP_TRY(hipSetDevice(e->device));
   if ((rc = bc_engine_sync(e)) != BC_OK) return rc;  // the submits, as bc_engine_finish waits for them
   if ((rc = ensure_raw_sorted(e, t_space, S)) != BC_OK) return rc;
-  if (n_cols == 0 || e->raw_n == 0 || G == 0) return BC_OK;
+  if (n_cols == 0 || e->raw_rows.n == 0 || G == 0) return BC_OK;
   if ((rc = ensure_render_pool(e, who)) != BC_OK) return rc;
   if ((rc = ensure_canon(e, who)) != BC_OK) return rc;
+  if ((rc = describe_groups(e, who, cg)) != BC_OK) return rc;
   bc::RawEnrichProj proj;
   bc::RawEnrichView v;
   memset(&proj, 0, sizeof proj);
   memset(&v, 0, sizeof v);
-  proj.canon = e->d_canon;
+  proj.canon = e->labels.d_canon;
   proj.S = v.S = S;
   proj.G = v.G = G;
   v.kind = (uint32_t)kind;
   v.merged = merged ? 1u : 0u;
-  v.sample = n_cols ? cols[0] : 0u;
-  v.n_cols = n_cols;
-  uint32_t longest[2] = {0, 0};  // the two longest fields of different groups
+  v.sample = cols[0];
+  memcpy(v.raw_len, cg.raw_len, sizeof v.raw_len);
+  memcpy(v.off_start, cg.off_start, sizeof v.off_start);
+  memcpy(v.radix, cg.radix, sizeof v.radix);
+  memcpy(proj.radix, cg.radix, sizeof proj.radix);
   uint32_t canon_off = 0;
   for (uint32_t g = 0; g < G; ++g) {
-    const DevGroup& Gr = P.groups[g0 + g];
-    uint32_t m;
+    proj.known[g] = cg.raw_len[g] ? 0u : 1u;
     proj.canon_off[g] = canon_off;
-    if (Gr.mode == kSetNone) {
-      v.raw_len[g] = m = Gr.len;
-      v.radix[g] = 1;
-      for (uint32_t b = 0; b < Gr.len; ++b) v.radix[g] *= 5;
-    } else {
-      if (bc_plan_n_counted(e->src_plan, g) != Gr.n_refs) {  // (cannot happen: the key's digits are the plan's sets)
-        set_error(std::string(who) + ": the plan's sets changed after the engine was created");
-        return BC_ERR_STATE;
-      }
-      proj.known[g] = 1u;
-      v.radix[g] = Gr.n_refs;
-      v.off_start[g] = e->label_off_start[g];
-      m = e->label_max[g];
-    }
-    proj.radix[g] = v.radix[g];
     canon_off += bc_plan_n_counted(e->src_plan, g);  // (ensure_canon lays the sets out back to back)
-    if (m > longest[0]) {
-      longest[1] = longest[0];
-      longest[0] = m;
-    } else if (m > longest[1]) {
-      longest[1] = m;
-    }
   }
-  const uint64_t max_line = 1 + (G - 1) + 21ull * n_cols + longest[0] + (kind == BC_ENRICH_DOUBLE ? longest[1] : 0u);
-  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;
-  const int k = kind == BC_ENRICH_SINGLE ? 0 : 1;
-  if ((rc = ensure_raw_enrich(e, k, proj)) != BC_OK) return rc;
-  if (e->re_n[k] == 0) return BC_OK;
-  ScratchGuard g;
-  uint32_t* d_cols = nullptr;
-  if ((rc = upload_cols(e, g, cols, n_cols, d_cols)) != BC_OK) return rc;
-  v.n = e->re_n[k];
-  v.n_seg = e->re_segs[k];
-  v.keys = (const uint64_t*)e->d_re[k];
+  const uint64_t max_line = enrich_max_line(G, cg.longest, n_cols, kind);
+  if ((rc = check_max_line(who, max_line)) != BC_OK) return rc;  // (before anything is built for a refused request)
+  const RawEnrichSegs& R = e->raw_enrich[kind == BC_ENRICH_SINGLE ? 0 : 1];
+  if ((rc = ensure_raw_enrich(e, kind == BC_ENRICH_SINGLE ? 0 : 1, proj)) != BC_OK) return rc;
+  if (R.n == 0) return BC_OK;
+  v.n = R.n;
+  v.n_seg = R.n_seg;
+  v.keys = (const uint64_t*)R.d;
   v.sums = v.keys + v.n;
   v.seg_start = v.sums + v.n;
-  v.cols = d_cols;
-  v.label_off = e->d_label_off;
-  v.label_bytes = e->d_label_bytes;
-  return stream_text(e, who, v, max_line, fn, user, n_rows);
+  return render_lines(e, who, v, max_line, cols, n_cols, fn, user, n_rows);
 }
 
 extern "C" {

@@ -1,11 +1,12 @@
 // bc_text_kernels.h -- the kernels that turn a key space into text lines, for every view that has lane code for it
 // (bc_render.h: the counts files; bc_enrich_render.h: the Single / Double files; bc_raw_render.h: the counts files of a
-// raw-key plan; bc_wide_render.h: those of a wide-key plan).  A view V gives, in namespace bc,
+// raw-key plan; bc_wide_render.h: those of a wide-key plan; bc_raw_enrich_render.h: the Single / Double files of a
+// raw-key plan -- all five written with bc_line.h).  A view V gives, in namespace bc,
 //     text_keys(v)                         the number of keys
 //     text_line_len(v, k)                  bytes of key k's line, 0: no line
 //     text_line_write(v, k, len, dst, at, win)   the part of the line inside a window
 // Device code and its launchers, all enqueueing on `stream`; included by bc_text.hip, which instantiates them for the
-// four views.
+// five views.
 //
 // A workgroup of four wavefronts owns a block of 1024 consecutive keys, a wavefront four chunks of 64 (one key per
 // lane, so every column's read is coalesced).  Chunks without a line are skipped by ballot.
@@ -24,7 +25,7 @@
 
 #include <algorithm>
 
-#include "bc_render.h"
+#include "bc_intrin.h"
 
 namespace bc {
 

@@ -25,11 +25,11 @@
 //     merged view       position i has a line when it is the first of its run of equal tuples (the payload with the
 //                       sample field masked; at most S entries, ascending in s) and some listed sample counts
 // and the line is bc_raw_render.h's, byte for byte:  f_0,f_1,..,f_{G-1},c_0,c_1,..\n  -- measured and written from its
-// END backwards.
+// END backwards (bc_line.h).
 #ifndef BC_WIDE_RENDER_H
 #define BC_WIDE_RENDER_H
 
-#include "bc_raw_render.h"
+#include "bc_line.h"
 
 namespace bc {
 
@@ -198,7 +198,7 @@ BC_HD uint32_t wide_row_len(const WideRenderView& v, uint64_t i) {
   for (uint32_t c = 0; c < v.n_cols; ++c) {
     const uint32_t x = wide_col_count(v, i, e, c);
     any |= x;
-    len += 1u + render_digits(x);  // ",count"
+    len += 1u + digits_u32(x);  // ",count"
   }
   if (v.merged && !any) return 0;
   for (uint32_t g = 0; g < v.G; ++g) {
@@ -214,55 +214,37 @@ BC_HD uint32_t wide_row_len(const WideRenderView& v, uint64_t i) {
 }
 
 // Writes the part of position i's line (len = wide_row_len, not 0) that falls into the window dst[0 .. win); the line
-// starts at window position `at`, which may be negative or beyond the window (render_row_write's contract).
+// starts at window position `at` (bc_line.h).
 template <typename Byte>
 BC_HD void wide_row_write(const WideRenderView& v, uint64_t i, uint32_t len, Byte* dst, int64_t at, uint32_t win) {
   uint64_t e;
   (void)wide_has_line(v, i, e);
   const uint64_t* pay = wide_payload(v, i);
-  int64_t p = at + (int64_t)len;  // one past the byte written next (the line is written backwards)
-#define BC_WIDE_PUT(ch)                                   \
-  do {                                                    \
-    --p;                                                  \
-    if (p >= 0 && p < (int64_t)win) dst[p] = (Byte)(ch);  \
-  } while (0)
-  BC_WIDE_PUT('\n');
-  for (uint32_t c = v.n_cols; c-- > 0;) {
-    uint32_t x = wide_col_count(v, i, e, c);
-    do {
-      const uint32_t q = x / 10u;  // (a multiplication: the divisor is a constant)
-      BC_WIDE_PUT('0' + (x - q * 10u));
-      x = q;
-    } while (x);
-    BC_WIDE_PUT(',');
+  LineCursor<Byte> c(dst, at, len, win);
+  c.put('\n');
+  for (uint32_t k = v.n_cols; k-- > 0;) {
+    c.put_u32(wide_col_count(v, i, e, k));
+    c.put(',');
   }
   for (uint32_t g = v.G; g-- > 0;) {
     if (v.raw_len[g]) {
-      // the capture lies at [p - n, p): base k at p - n + k, read from the planes 32 bases at a time
+      // the capture lies at [p, p + n) once reserved: base k at p + k, read from the planes 32 bases at a time
       const uint32_t n = v.raw_len[g];
-      p -= (int64_t)n;
+      c.reserve(n);
       for (uint32_t k0 = 0; k0 < n; k0 += 32u) {
         const uint32_t cnt = n - k0 < 32u ? n - k0 : 32u;
-        if (p + (int64_t)(k0 + cnt) <= 0 || p + (int64_t)k0 >= (int64_t)win) continue;  // (all of it outside the window)
+        if (c.p + (int64_t)(k0 + cnt) <= 0 || c.p + (int64_t)k0 >= (int64_t)win) continue;  // (all of it outside the window)
         const uint32_t b = v.key_bit[g] + k0;
         const uint64_t p1 = wide_bits(pay, b, cnt), p2 = wide_bits(pay, b + n, cnt), pn = wide_bits(pay, b + 2u * n, cnt);
-        for (uint32_t j = 0; j < cnt; ++j) {
-          const int64_t w = p + (int64_t)(k0 + j);
-          if (w >= 0 && w < (int64_t)win) dst[w] = (Byte)raw_base_char(wide_base_code(p1, p2, pn, j));
-        }
+        for (uint32_t j = 0; j < cnt; ++j) c.store(c.p + (int64_t)(k0 + j), raw_base_char(wide_base_code(p1, p2, pn, j)));
       }
     } else {
       uint32_t n;
       const uint32_t a = wide_label(v, i, g, n);
-      int64_t lo = p - (int64_t)n, hi = p;
-      p = lo;
-      if (lo < 0) lo = 0;
-      if (hi > (int64_t)win) hi = (int64_t)win;
-      for (int64_t w = lo; w < hi; ++w) dst[w] = (Byte)v.label_bytes[a + (uint32_t)(w - p)];
+      c.put_label(v.label_bytes, a, n);
     }
-    if (g) BC_WIDE_PUT(',');
+    if (g) c.put(',');
   }
-#undef BC_WIDE_PUT
 }
 
 // the names bc_text_kernels.h reaches a view's lane code by

@@ -1,5 +1,6 @@
-// stage_check -- what the three render harnesses (render_host, raw_render_host, enrich_render_host) do with a view once
-// its input is parsed, through the names bc_text_kernels.h reaches a view's lane code by.  TEST-ONLY.
+// stage_check -- what the five render harnesses (render_host, raw_render_host, wide_render_host, enrich_render_host,
+// raw_enrich_render_host) do with a view once its input is parsed, through the names bc_text_kernels.h reaches a view's
+// lane code by.  TEST-ONLY.
 //
 // Every line is written twice: whole, into a heap block of exactly text_line_len bytes (AddressSanitizer sees a byte
 // outside it, a NUL left in it is a byte not written), and the way a wavefront stages it -- the lines of 64 keys laid
